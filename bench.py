@@ -5,12 +5,20 @@ compute, fp32 master weights + AdamW moments (sharded), synthetic token data,
 random-init weights. Weak scaling: ``--micro-batch`` sequences of ``--seq`` tokens
 per GPU per step.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0. ``--model resnet50`` runs the secondary headline
 (ResNet50 bf16 images/s, DP).
+
+A plain run does only what the headline figure needs: set up, warm up, time ``--steps`` steps,
+print the result line. ``--dump-outputs DIR`` also writes what the last timed step computed
+(``DIR/<name>.npy``, float32) so two builds can be compared output for output: the inputs and
+the initial weights are seeded, so they are identical from run to run. ``--full`` is where
+measurements beyond the headline figure belong (runs of their own: other precisions or
+configurations, reference comparisons, per-kernel figures); the benchmark has none today, so
+the option changes nothing yet.
 """
 import argparse
 import json
@@ -38,6 +46,12 @@ def parse():
     p.add_argument('--no-graph', action='store_true',
                    help='BERT: run the static Executor op by op (no HIP-graph replay)')
     p.add_argument('--profile-dir', default=None)
+    p.add_argument('--dump-outputs', default=None, metavar='DIR',
+                   help='after the timed steps write what the last timed step computed as '
+                        'DIR/<name>.npy (float32; a fixed seeded sample of large outputs)')
+    p.add_argument('--full', action='store_true',
+                   help='also run the measurements beyond the headline figure (none today: a plain '
+                        'run already does only what its result line needs)')
     p.add_argument('--tuned-gemms', action='store_true',
                    help='load the committed MI355X TunableOp solutions for the library GEMMs (off by '
                         'default: measured 126.93 vs 126.93 ms per GPT step, profiles/r6/tunableop_ab.md)')
@@ -178,6 +192,42 @@ def _timed(step_fn, a, torch, dist, world, dev):
     return dt
 
 
+_DUMP_SAMPLE = 2048  # elements kept per parameter (GPT-3 1.3B: 292 parameters -> 2.4 MB)
+
+
+def _param_sample(params, torch):
+    """A fixed, seeded sample of every parameter as one float32 vector: the same positions in
+    every run and every build (the index stream depends only on the parameter sizes)."""
+    g = torch.Generator().manual_seed(20240229)
+    out = []
+    for p in params:
+        t = getattr(p, '_t', p).detach().reshape(-1)
+        if t.numel() == 0:
+            continue
+        if t.numel() > _DUMP_SAMPLE:
+            t = t[torch.randint(0, t.numel(), (_DUMP_SAMPLE,), generator=g).to(t.device)]
+        out.append(t.float().cpu())
+    return torch.cat(out) if out else torch.zeros(0)
+
+
+def _dump_outputs(a, rank, torch, outputs):
+    """``--dump-outputs DIR``: rank 0 writes ``DIR/<name>.npy`` (float32) for every entry of
+    ``outputs`` (name -> tensor / array / number)."""
+    if not a.dump_outputs or rank != 0:
+        return
+    import numpy as np
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    total = 0
+    for name, v in outputs.items():
+        v = getattr(v, '_t', v)
+        if torch.is_tensor(v):
+            v = v.detach().float().cpu().numpy()
+        arr = np.atleast_1d(np.asarray(v, dtype=np.float32))
+        total += arr.nbytes
+        np.save(os.path.join(a.dump_outputs, name + '.npy'), arr)
+    assert total <= 64 << 20, f'--dump-outputs wrote {total} bytes (limit 64 MiB)'
+
+
 def _op_profile(step_fn, a, torch, rank):
     """One extra (untimed) step under torch.profiler with Python stacks: per-op tables grouped
     by call site (which layer issues each fill / copy / reduce kernel)."""
@@ -227,6 +277,11 @@ def bench_gpt(a, paddle, torch, dist, C, world, rank, dev):
         losses.append(loss.detach())
 
     dt = _timed(step, a, torch, dist, world, dev)
+    if a.dump_outputs:
+        # what a caller of the step receives: its loss, and the parameters it updated in place
+        _dump_outputs(a, rank, torch, {'loss': losses[-1],
+                                       'losses': torch.stack([l._t.float().reshape(()) for l in losses[-a.steps:]]),
+                                       'params_sample': _param_sample(model.parameters(), torch)})
     if a.profile_dir:
         _op_profile(step, a, torch, rank)
     last_loss = float(losses[-1].item())
@@ -275,14 +330,19 @@ def bench_resnet(a, paddle, torch, dist, C, world, rank, dev):
     x = paddle.Tensor(torch.randn(bs, 224, 224, 3, device=dev, dtype=torch.bfloat16))
     y = paddle.Tensor(torch.randint(0, 1000, (bs,), device=dev))
     ce = paddle.nn.CrossEntropyLoss()
+    last = [None]
 
     def step():
         loss = ce(model(x), y)
         loss.backward()
         opt.step()
         opt.clear_grad()
+        last[0] = loss.detach()
 
     dt = _timed(step, a, torch, dist, world, dev)
+    if a.dump_outputs:
+        _dump_outputs(a, rank, torch, {'loss': last[0],
+                                       'params_sample': _param_sample(model.parameters(), torch)})
     if a.profile_dir:
         _op_profile(step, a, torch, rank)
     graphed = hasattr(model, 'forward') and hasattr(model.forward, 'graph_status')
@@ -348,6 +408,8 @@ def bench_ernie(a, paddle, torch, dist, C, world, rank, dev):
             opt.clear_grad()
 
     dt = _timed(step, a, torch, dist, world, dev)
+    if a.dump_outputs:
+        _dump_outputs(a, rank, torch, {'params_sample': _param_sample(pl.parameters(), torch)})
     tps = B * S * a.steps / dt
     n_params = sum(int(np.prod(p.shape)) for p in pl.parameters()) * mp
     return {"metric": "tokens/sec ERNIE-3.0-10B Fleet TP x PP", "value": round(tps, 2),
@@ -419,6 +481,9 @@ def bench_bert(a, paddle, torch, dist, C, world, rank, dev):
         last[0] = exe.run(prog, feed=feed, fetch_list=[loss_v], return_numpy=False)[0]
 
     dt = _timed(step, a, torch, dist, world, dev)
+    if a.dump_outputs:
+        _dump_outputs(a, rank, torch, {'loss': last[0],
+                                       'params_sample': _param_sample(model.parameters(), torch)})
     if a.profile_dir:
         _op_profile(step, a, torch, rank)   # per-op tables need --no-graph (a graph replay is one op)
     paddle.disable_static()

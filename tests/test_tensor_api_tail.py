@@ -1,7 +1,7 @@
 """Tensor-API names the reference exports that were missing (parity:
 python/paddle/tensor/__init__.py tensor_method_func, python/paddle/__init__.py __all__):
 rank, create_tensor and the in-place erfinv_ / remainder_ / lerp_ / put_along_axis_."""
-import re
+import os
 
 import numpy as np
 import torch
@@ -40,11 +40,10 @@ def test_inplace_variants_match_out_of_place():
 
 
 def test_reference_tensor_method_names_present():
-    src = open('/root/reference/python/paddle/tensor/__init__.py').read() \
-        if __import__('os').path.exists('/root/reference/python/paddle/tensor/__init__.py') else None
-    if src is None:
-        return
-    m = re.search(r"tensor_method_func\s*=\s*\[(.*?)\]", src, re.S)
-    names = re.findall(r"'(\w+)'", m.group(1))
+    # the reference's list is stored with the tests: no file outside the repository is read
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'tensor_method_names.txt')
+    with open(golden) as f:
+        names = [n for line in f if not line.startswith('#') for n in line.split()]
+    assert len(names) > 200
     missing = [n for n in names if not hasattr(paddle, n) and not hasattr(paddle.Tensor, n)]
     assert missing == [], missing
