@@ -211,6 +211,12 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
       ``cache_kvs`` ([2, B, H, max_len, D] per layer) the prompt's K/V written in place.
     * decode phase (``time_step`` = t, x [B, 1, E]): the HIP decode-attention kernel streams
       cache positions [0, t) split-K across the chip and appends the token's K/V at t.
+      With ``seq_lens`` ([B] int) the batch is ragged: ``seq_lens[b]`` is the number of cache
+      positions already filled for sequence ``b`` (any ``pre_caches`` prefix included), i.e.
+      the position its token is written at; it attends over [0, seq_lens[b]] only.
+      ``time_step`` stays the phase switch and the batch-wide upper bound (max of seq_lens).
+      ``rotary_embs`` ([2, B, 1, 1, D], each sequence's own position) is applied inside the
+      kernel when the head dim allows it, else by the torch rotation before it.
     * every residual add + dropout + following LayerNorm is ONE add_dropout_layer_norm
       kernel; FFN1 runs with its bias+activation in the GEMM epilogue.
     Returns ``out`` or ``(out, cache_kvs)`` when caches are given (updated in place)."""
@@ -229,10 +235,13 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
         t = int(time_step) if decode else None
     if decode and S != 1:
         raise ValueError("fused_multi_transformer: decode phase (time_step given) takes one token")
-    rot = None
+    rot = krot = None
     if rotary_embs is not None and rotary_emb_dims:
         re = _u(rotary_embs)                          # [2, B, 1, S, D]
-        rot = (re[0].reshape(B, S, -1), re[1].reshape(B, S, -1))
+        if decode and K.rotary_in_kernel(re.shape[-1], rotary_emb_dims):
+            krot = re.reshape(2, B, -1)               # rotated inside the decode kernel
+        else:
+            rot = (re[0].reshape(B, S, -1), re[1].reshape(B, S, -1))
     mask = _t(attn_mask)
     sl = _t(seq_lens)
     zero_b = torch.zeros(E, dtype=h.dtype, device=h.device)
@@ -255,7 +264,9 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
         if decode:
             if cache is None:
                 raise ValueError("fused_multi_transformer: time_step needs cache_kvs")
-            o = K.mmha_decode(qkv[:, 0].contiguous(), cache, t, mask).reshape(B, 1, H * D)
+            o = K.mmha_decode(qkv[:, 0].contiguous(), cache, t, mask, seq_lens=sl, rotary=krot,
+                              rotary_dims=rotary_emb_dims if krot is not None else 0
+                              ).reshape(B, 1, H * D)
         else:
             q, k, v = qkv.unbind(2)                  # [B, S, H, D]
             P = 0

@@ -134,7 +134,8 @@ class FusedMultiTransformer(Layer):
     the reference layout (parity: python/paddle/incubate/nn/layer/fused_transformer.py
     FusedMultiTransformer): qkv [3, H, D, E], linear [E, E], ffn1 [E, F], ffn2 [F, E].
     ``forward(src, attn_mask, caches, ..., time_step)`` runs the context phase (caches
-    filled in place) or, with ``time_step``, one decode step on the HIP cache kernel."""
+    filled in place) or, with ``time_step``, one decode step on the HIP cache kernel; there
+    ``seq_lens`` ([B], cache positions already filled per sequence) makes the batch ragged."""
 
     def __init__(self, embed_dim, num_heads, dim_feedforward, dropout_rate=0.0, activation="gelu",
                  normalize_before=True, ln_scale_attrs=None, ln_bias_attrs=None,
@@ -204,6 +205,14 @@ class FusedMultiTransformerDecoder:
         h = dec.prefill(prompt_hidden)          # [B, S0, E], fills the caches
         for _ in range(n): h_t = dec.step(x_t)  # [B, 1, E] -> [B, 1, E]
     ``attn_mask`` (additive, [B, max_seq_len]) masks padded positions across all steps.
+
+    Ragged batches: ``prefill(x, seq_lens=lens)`` takes right-padded prompts; every sequence
+    then continues at its own position (``self.lens``, a device int32 [B] counter that the
+    captured graph advances together with ``self.t`` = max(lens); only a ragged prefill
+    makes it live), so one graph still serves the whole batch and a short sequence streams
+    only its own part of the cache.
+    ``set_rotary(cos, sin, rotary_emb_dims)`` installs [max_seq_len, D] rotary tables: prefill
+    uses rows [0, S0), each step gathers every sequence's row by its current position.
     """
 
     def __init__(self, model, batch_size, max_seq_len, use_graph=True):
@@ -217,6 +226,10 @@ class FusedMultiTransformerDecoder:
         self.caches = [torch.zeros(2, self.B, H, self.L, D, device=self.dev, dtype=self.dtype)
                        for _ in range(n)]
         self.t = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self.lens = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
+        self.ragged = False
+        self.rot = None               # [2, max_seq_len, D] fp32 (cos, sin)
+        self.rot_dims = 0
         self.mask = torch.zeros(self.B, 1, 1, self.L, dtype=torch.float32, device=self.dev)
         self.x_buf = torch.zeros(self.B, 1, E, device=self.dev, dtype=self.dtype)
         self.use_graph = use_graph and self.dev.type == 'cuda'
@@ -232,8 +245,20 @@ class FusedMultiTransformerDecoder:
         m = attn_mask._t if hasattr(attn_mask, '_t') else torch.as_tensor(attn_mask)
         self.mask.copy_(m.reshape(self.B, 1, 1, self.L).to(self.mask.dtype))
 
-    def prefill(self, x, attn_mask=None):
-        """Context phase over the prompt (caches filled in place); decode continues at S0."""
+    def set_rotary(self, cos, sin, rotary_emb_dims):
+        """Rotary tables ``cos`` / ``sin`` [max_seq_len, D] (row p = position p) for prefill and
+        every later step. Call it before ``prefill``: the step graph is captured with it."""
+        import torch
+        D = self.model.head_dim
+        tab = torch.stack([torch.as_tensor(c._t if hasattr(c, '_t') else c).reshape(self.L, D)
+                           for c in (cos, sin)])
+        self.rot = tab.to(device=self.dev, dtype=torch.float32).contiguous()
+        self.rot_dims = int(rotary_emb_dims)
+        self._graph = None
+
+    def prefill(self, x, attn_mask=None, seq_lens=None):
+        """Context phase over the prompt (caches filled in place); decode continues at S0, or
+        with ``seq_lens`` ([B], right-padded prompts) at every sequence's own length."""
         from ...framework.core import Tensor
         import torch
         xt = x._t if hasattr(x, '_t') else x
@@ -241,16 +266,46 @@ class FusedMultiTransformerDecoder:
         if attn_mask is None:
             m = torch.triu(torch.full((S0, S0), float('-inf'), device=self.dev), 1)
             attn_mask = Tensor(m.expand(self.B, 1, S0, S0).to(self.dtype))
+        kw = {}
+        if self.rot is not None:
+            r = self.rot[:, :S0]                           # [2, S0, D], the same for every b
+            kw = dict(rotary_embs=Tensor(r[:, None, None].expand(2, self.B, 1, S0, r.shape[-1])),
+                      rotary_emb_dims=self.rot_dims)
+        ragged = seq_lens is not None
+        if ragged:
+            sl = seq_lens._t if hasattr(seq_lens, '_t') else torch.as_tensor(seq_lens)
+            sl = sl.reshape(self.B).to(device=self.dev, dtype=torch.int32)
+            kw['seq_lens'] = Tensor(sl)
         with torch.no_grad():
-            out, _ = self.model(Tensor(xt), attn_mask=attn_mask, caches=self._caches())
-        self.t.fill_(S0)
+            out, _ = self.model(Tensor(xt), attn_mask=attn_mask, caches=self._caches(), **kw)
+        if ragged:
+            self.lens.copy_(sl)
+            self.t.copy_(sl.max().reshape(1))
+        else:
+            self.lens.fill_(S0)
+            self.t.fill_(S0)
+        if ragged != self.ragged:
+            self.ragged, self._graph = ragged, None      # the other graph
         return out
 
     def _step_eager(self):
         from ...framework.core import Tensor
+        kw = {}
+        if self.ragged:
+            kw['seq_lens'] = Tensor(self.lens)
+        if self.rot is not None:
+            # every sequence's own row: its position when ragged, else the common one
+            r = self.rot.index_select(1, self.lens if self.ragged else self.t)
+            r = r.expand(2, self.B, r.shape[-1])
+            kw.update(rotary_embs=Tensor(r[:, :, None, None]), rotary_emb_dims=self.rot_dims)
         out, _ = self.model(Tensor(self.x_buf), attn_mask=Tensor(self.mask), caches=self._caches(),
-                            time_step=Tensor(self.t))
+                            time_step=Tensor(self.t), **kw)
         return out._t
+
+    def _advance(self):
+        self.t.add_(1)
+        if self.ragged:               # the uniform graph stays as it was: one counter
+            self.lens.add_(1)
 
     def step(self, x_tok):
         """One token for every sequence: returns [B, 1, E]; the position advances by one."""
@@ -261,7 +316,7 @@ class FusedMultiTransformerDecoder:
         with torch.no_grad():
             if not self.use_graph:
                 out = self._step_eager()
-                self.t.add_(1)
+                self._advance()
                 return Tensor(out)
             if self._graph is None:
                 s = torch.cuda.Stream()
@@ -272,7 +327,7 @@ class FusedMultiTransformerDecoder:
                 self._graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(self._graph):
                     self._out = self._step_eager()
-                    self.t.add_(1)
+                    self._advance()
             self._graph.replay()
         return Tensor(self._out.clone())
 

@@ -33,7 +33,7 @@ void pra_vp_ce_bwd(const void*, const int64_t*, const float*, const float*, void
 const char* pra_build_info();
 int pra_mmha_splits(int, int, int);
 int pra_mmha_decode(const void*, void*, const float*, float*, void*, int, int, int, int, int, const int*, int, int,
-                    float, int, hipStream_t);
+                    float, int, const int*, const float*, int, hipStream_t);
 void pra_bias_gelu_fwd(const void*, const void*, void*, int64_t, int, int, int, hipStream_t);
 void pra_bias_gelu_bwd(const void*, const void*, const void*, void*, int64_t, int, int, int, hipStream_t);
 void pra_adamw_mt(const int64_t*, const float*, const int64_t*, int, float, float, float, float, float, float, float,
@@ -261,10 +261,12 @@ PYBIND11_MODULE(_pra_hip, m) {
   });
   m.def("mmha_splits", [](int B, int H, int t) { return pra_mmha_splits(B, H, t); });
   m.def("mmha_decode", [](P qkv, P cache, P mask, P ws, P out, int B, int H, int L, int D, int t, P t_dev,
-                          int splits, int mask_len, float scale, int dt, P s) {
+                          int splits, int mask_len, float scale, int dt, P s, P seq_lens, P rot, int rot_dims) {
     if (pra_mmha_decode(CV(qkv), V(cache), CF(mask), F(ws), V(out), B, H, L, D, t,
-                        reinterpret_cast<const int*>(t_dev), splits, mask_len, scale, dt, S(s)) != 0)
-      throw std::invalid_argument("mmha_decode: unsupported head_dim/dtype or time_step out of range");
+                        reinterpret_cast<const int*>(t_dev), splits, mask_len, scale, dt,
+                        reinterpret_cast<const int*>(seq_lens), CF(rot), rot_dims, S(s)) != 0)
+      throw std::invalid_argument(
+          "mmha_decode: unsupported head_dim/dtype/rotary_dims or time_step out of range");
     check_launch("mmha_decode");
   });
   m.def("bias_gelu_fwd", [](P x, P b, P y, int64_t rows, int cols, int dt, int approx, P s) {

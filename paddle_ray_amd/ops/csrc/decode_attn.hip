@@ -18,6 +18,14 @@
 //    per lane are in flight.
 //  * the new token's K/V never round-trips through the cache: the workgroup that owns
 //    position t uses them from the qkv buffer and writes them into the cache (vector stores).
+//  * ragged batches (EXT instantiation; the plain one is compiled without any of it):
+//    seq_lens[b] replaces t for sequence b, so a short sequence streams only its own
+//    [0, t_b) and workgroups whose key range lies past t_b leave at once with the empty
+//    partial (m = -inf, l = 0). rot [2, B, D] (cos, sin) rotates q and the new k in registers
+//    (half-split rule inside each of rot_dims chunks; the partner 8 dims are one more 16-byte
+//    load of the same qkv row). The rotated k is rounded to the cache dtype once and that
+//    value is both stored at t_b and scored against, so later steps that read the row back
+//    agree with this one.
 #include "common.h"
 
 namespace pra {
@@ -45,7 +53,20 @@ __device__ __forceinline__ void merge(float& m, float& l, float* a, float m2, fl
   m = M;
 }
 
-template <typename T, int D>
+// x[8] (dims d0..d0+7 of one head row) rotated against its partner half a chunk away
+template <typename T>
+__device__ __forceinline__ void rotate8(const T* row, int d0, int chunk, const float* cs, const float* sn, float* x) {
+  const int half = chunk >> 1;
+  const bool left = (d0 % chunk) < half;
+  float p[8], c[8], s[8];
+  load8<T>(row + (left ? d0 + half : d0 - half), p);
+  load8<float>(cs + d0, c);
+  load8<float>(sn + d0, s);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) x[i] = left ? x[i] * c[i] - p[i] * s[i] : x[i] * c[i] + p[i] * s[i];
+}
+
+template <typename T, int D, bool EXT>
 __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
     const T* __restrict__ qkv,      // [B, 3, H, D] (bias already added)
     T* __restrict__ cache,          // [2, B, H, L, D]
@@ -54,17 +75,27 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
     float* __restrict__ ws_acc,     // [B, H, S, D]
     T* __restrict__ out,            // [B, H, D] (used when splits == 1)
     int B, int H, int L, int t_host, const int* __restrict__ t_dev, int keys_per_split, int mask_len,
-    float scale) {
+    float scale,
+    const int* __restrict__ seq_lens,  // EXT: [B] per-sequence position, or null
+    const float* __restrict__ rot,     // EXT: [2, B, D] cos then sin, or null
+    int rot_dims) {
   // t_dev (HIP-graph decode loops): the position comes from device memory, so one captured
   // graph serves every step; an out-of-range position writes nothing and outputs zeros
-  const int t = t_dev ? t_dev[0] : t_host;
+  int t = t_dev ? t_dev[0] : t_host;
   constexpr int G = D / 8;            // lanes per key
   constexpr int KPW = 64 / G;         // keys per wave per sub-step
   const int split = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   const int splits = gridDim.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int gl = lane % G, grp = lane / G;
-  const bool t_ok = t >= 0 && t < L && !(mask && mask_len < t + 1);
+  bool in_bound = true;
+  if constexpr (EXT) {
+    if (seq_lens) {  // this sequence's own position; t_host / t_dev stay the bound that sized the grid
+      t = seq_lens[b];
+      in_bound = t_dev || t <= t_host;  // a device bound means the splits cover all of L
+    }
+  }
+  const bool t_ok = in_bound && t >= 0 && t < L && !(mask && mask_len < t + 1);
   const int lo = split * keys_per_split;
   const int hi = t_ok ? min(t + 1, lo + keys_per_split) : lo;
 
@@ -75,16 +106,47 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
   T* kc = cache + ((size_t)b * H + h) * (size_t)L * D;
   T* vc = cache + (BH + (size_t)b * H + h) * (size_t)L * D;
 
-  if (t_ok && t >= lo && t < hi && wave == 0 && grp == 0) {  // append the new token to the cache
-    float kv[8];
-    load8<T>(knew + gl * 8, kv);
-    store8<T>(kc + (size_t)t * D + gl * 8, kv);
-    load8<T>(vnew + gl * 8, kv);
-    store8<T>(vc + (size_t)t * D + gl * 8, kv);
-  }
-
   float q[8];
-  load8<T>(qrow + gl * 8, q);
+  float kt[8];  // EXT: the token's own k exactly as the cache holds it
+  if constexpr (EXT) {
+    if (hi <= lo) {  // a key range past t_b, or a guarded position: no loads, the empty partial
+      if (wave == 0 && grp == 0) {
+        if (splits == 1) {
+          const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+          store8<T>(out + ((size_t)b * H + h) * D + gl * 8, z);
+        } else if (gl == 0) {
+          *reinterpret_cast<float2*>(ws_ml + (((size_t)b * H + h) * splits + split) * 2) =
+              make_float2(-INFINITY, 0.f);
+        }
+      }
+      return;
+    }
+    load8<T>(qrow + gl * 8, q);
+    load8<T>(knew + gl * 8, kt);
+    if (rot) {
+      const float* cs = rot + (size_t)b * D;
+      const float* sn = rot + ((size_t)B + b) * D;
+      rotate8<T>(qrow, gl * 8, D / rot_dims, cs, sn, q);
+      rotate8<T>(knew, gl * 8, D / rot_dims, cs, sn, kt);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) kt[i] = Cvt<T>::to(Cvt<T>::from(kt[i]));  // rounded once
+    }
+    if (t < hi && wave == 0 && grp == 0) {  // append the new token (here hi > lo, so t_ok and t >= lo)
+      float v[8];
+      store8<T>(kc + (size_t)t * D + gl * 8, kt);
+      load8<T>(vnew + gl * 8, v);
+      store8<T>(vc + (size_t)t * D + gl * 8, v);
+    }
+  } else {
+    if (t_ok && t >= lo && t < hi && wave == 0 && grp == 0) {  // append the new token to the cache
+      float kv[8];
+      load8<T>(knew + gl * 8, kv);
+      store8<T>(kc + (size_t)t * D + gl * 8, kv);
+      load8<T>(vnew + gl * 8, kv);
+      store8<T>(vc + (size_t)t * D + gl * 8, kv);
+    }
+    load8<T>(qrow + gl * 8, q);
+  }
 #pragma unroll
   for (int i = 0; i < 8; ++i) q[i] *= scale;
 
@@ -105,6 +167,12 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
       const T* vp = (kk == t) ? vnew : vc + (size_t)kk * D;
       load8<T>(kp + gl * 8, kx[u]);
       load8<T>(vp + gl * 8, vx[u]);
+      if constexpr (EXT) {  // the token's own key: the (rotated, rounded) registers, not the raw row
+        if (kk == t) {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) kx[u][i] = kt[i];
+        }
+      }
     }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -181,13 +249,20 @@ __global__ void __launch_bounds__(D) mmha_combine_k(const float* __restrict__ ws
 
 template <typename T, int D>
 int launch(const void* qkv, void* cache, const float* mask, float* ws, void* out, int B, int H, int L, int t,
-           const int* t_dev, int splits, int mask_len, float scale, hipStream_t s) {
+           const int* t_dev, int splits, int mask_len, float scale, const int* seq_lens, const float* rot,
+           int rot_dims, hipStream_t s) {
   const int keys = t_dev ? L : t + 1;  // device position: splits cover the whole cache
   const int per = (keys + splits - 1) / splits;
   float* ws_ml = ws;
   float* ws_acc = ws + (((size_t)B * H * splits * 2 + 3) / 4) * 4;  // 16-B aligned
-  hipLaunchKernelGGL((mmha_split_k<T, D>), dim3(splits, H, B), dim3(kWaves * 64), 0, s, (const T*)qkv, (T*)cache,
-                     mask, ws_ml, ws_acc, (T*)out, B, H, L, t, t_dev, per, mask_len, scale);
+  if (seq_lens || rot)
+    hipLaunchKernelGGL((mmha_split_k<T, D, true>), dim3(splits, H, B), dim3(kWaves * 64), 0, s, (const T*)qkv,
+                       (T*)cache, mask, ws_ml, ws_acc, (T*)out, B, H, L, t, t_dev, per, mask_len, scale, seq_lens, rot,
+                       rot_dims);
+  else
+    hipLaunchKernelGGL((mmha_split_k<T, D, false>), dim3(splits, H, B), dim3(kWaves * 64), 0, s, (const T*)qkv,
+                       (T*)cache, mask, ws_ml, ws_acc, (T*)out, B, H, L, t, t_dev, per, mask_len, scale, nullptr,
+                       nullptr, 0);
   if (splits > 1)
     hipLaunchKernelGGL((mmha_combine_k<T, D>), dim3(H, B), dim3(D), 0, s, ws_ml, ws_acc, (T*)out, splits);
   return 0;
@@ -210,17 +285,24 @@ int pra_mmha_splits(int B, int H, int t) {
   return s;
 }
 
-// ws: fp32 workspace of B*H*splits*(2 + D) + 4 floats (unused when splits == 1)
+// ws: fp32 workspace of B*H*splits*(2 + D) + 4 floats (unused when splits == 1).
+// seq_lens (device int32 [B]) and rot (device fp32 [2, B, D], rot_dims chunks) are optional: null
+// runs the plain kernel. t / t_dev stay the batch-wide bound that the splits were sized for.
 int pra_mmha_decode(const void* qkv, void* cache, const float* mask, float* ws, void* out, int B, int H, int L,
-                    int D, int t, const int* t_dev, int splits, int mask_len, float scale, int dt, hipStream_t s) {
+                    int D, int t, const int* t_dev, int splits, int mask_len, float scale, int dt,
+                    const int* seq_lens, const float* rot, int rot_dims, hipStream_t s) {
   if (splits < 1) return -1;
   if (!t_dev && (t < 0 || t >= L || (mask && mask_len < t + 1))) return -1;
-#define PRA_MMHA(TT)                                                                                          \
-  switch (D) {                                                                                                \
-    case 64: return launch<TT, 64>(qkv, cache, mask, ws, out, B, H, L, t, t_dev, splits, mask_len, scale, s);        \
-    case 128: return launch<TT, 128>(qkv, cache, mask, ws, out, B, H, L, t, t_dev, splits, mask_len, scale, s);      \
-    case 256: return launch<TT, 256>(qkv, cache, mask, ws, out, B, H, L, t, t_dev, splits, mask_len, scale, s);      \
-    default: return -1;                                                                                       \
+  if (rot && (rot_dims < 1 || D % (16 * rot_dims) != 0)) return -1;  // a half chunk is whole 8-dim lanes
+#define PRA_MMHA(TT)                                                                                     \
+  switch (D) {                                                                                           \
+    case 64: return launch<TT, 64>(qkv, cache, mask, ws, out, B, H, L, t, t_dev, splits, mask_len, scale, \
+                                   seq_lens, rot, rot_dims, s);                                          \
+    case 128: return launch<TT, 128>(qkv, cache, mask, ws, out, B, H, L, t, t_dev, splits, mask_len, scale, \
+                                     seq_lens, rot, rot_dims, s);                                        \
+    case 256: return launch<TT, 256>(qkv, cache, mask, ws, out, B, H, L, t, t_dev, splits, mask_len, scale, \
+                                     seq_lens, rot, rot_dims, s);                                        \
+    default: return -1;                                                                                  \
   }
   if (dt == kBF16) { PRA_MMHA(bf16) }
   if (dt == kF16) { PRA_MMHA(f16) }

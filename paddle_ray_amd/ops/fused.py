@@ -714,24 +714,65 @@ def vocab_parallel_cross_entropy(logits, labels, pg=None, world=1, rank=0, ignor
 # multihead attention kernel of fused_multi_transformer). qkv [B, 3, H, D] is the current
 # token's projection, cache [2, B, H, L, D]; positions [0, t) are read from the cache, the
 # token's own K/V are written into it at position t. Inference only (no autograd).
+# Ragged batches: seq_lens [B] gives every sequence its own t_b (t stays the batch-wide upper
+# bound), rotary [2, B, D] (cos, sin) rotates q and the new k before anything else. A
+# sequence whose position is out of range gets a zero output and no cache write.
 # =============================================================================
+def _rotate_rows(x, cos, sin, dims):
+    """Half-split rotation inside each of ``dims`` chunks: x [B, H, D] fp32, cos/sin [B, D]."""
+    B, H, D = x.shape
+    last = D // dims
+    half = last // 2
+    xv = x.view(B, H, dims, last)
+    c, sn = cos.view(B, 1, dims, last), sin.view(B, 1, dims, last)
+    left, right = xv[..., :half], xv[..., half:]
+    return torch.cat([left * c[..., :half] - right * sn[..., :half],
+                      right * c[..., half:] + left * sn[..., half:]], -1).reshape(B, H, D)
+
+
 @R.register_kernel('mmha_decode', 'ref')
-def _mmha_ref(qkv, cache, t, mask):
+def _mmha_ref(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0):
+    L = cache.shape[3]
+    bound = L - 1  # a tensor position is a device position: no batch-wide bound below L
     if isinstance(t, torch.Tensor):
         t = int(t.reshape(-1)[0])
-    q, k, v = qkv.unbind(1)                                   # [B, H, D]
-    cache[0, :, :, t] = k
-    cache[1, :, :, t] = v
-    K_, V_ = cache[0, :, :, :t + 1].float(), cache[1, :, :, :t + 1].float()
-    s = torch.einsum('bhd,bhld->bhl', q.float(), K_) / math.sqrt(q.shape[-1])
-    if mask is not None:
-        s = s + mask.reshape(mask.shape[0], -1)[:, None, :t + 1].float()
-    p = torch.softmax(s, -1)
-    return torch.einsum('bhl,bhld->bhd', p, V_).to(qkv.dtype)
+    else:
+        bound = t
+    if seq_lens is None and rotary is None:
+        q, k, v = qkv.unbind(1)                                   # [B, H, D]
+        cache[0, :, :, t] = k
+        cache[1, :, :, t] = v
+        K_, V_ = cache[0, :, :, :t + 1].float(), cache[1, :, :, :t + 1].float()
+        s = torch.einsum('bhd,bhld->bhl', q.float(), K_) / math.sqrt(q.shape[-1])
+        if mask is not None:
+            s = s + mask.reshape(mask.shape[0], -1)[:, None, :t + 1].float()
+        p = torch.softmax(s, -1)
+        return torch.einsum('bhl,bhld->bhd', p, V_).to(qkv.dtype)
+    B, _, H, D = qkv.shape
+    q, k, v = qkv[:, 0].float(), qkv[:, 1].float(), qkv[:, 2]
+    if rotary is not None:
+        R._STATS[('mmha_decode_rotary', 'ref')] += 1
+        cos, sin = rotary.reshape(2, B, D).float().to(qkv.device)
+        q, k = _rotate_rows(q, cos, sin, rotary_dims), _rotate_rows(k, cos, sin, rotary_dims)
+    k = k.to(qkv.dtype)                                           # rounded once, as cached
+    lens = [t] * B if seq_lens is None else [int(x) for x in seq_lens.reshape(-1).tolist()]
+    mrows = None if mask is None else mask.reshape(B, -1).float()
+    out = torch.zeros(B, H, D, device=qkv.device, dtype=torch.float32)
+    for b, tb in enumerate(lens):
+        if not (0 <= tb < L and tb <= bound) or (mrows is not None and mrows.shape[1] < tb + 1):
+            continue                                              # guarded: zeros out, no write
+        cache[0, b, :, tb] = k[b]
+        cache[1, b, :, tb] = v[b]
+        K_, V_ = cache[0, b, :, :tb + 1].float(), cache[1, b, :, :tb + 1].float()
+        s = torch.einsum('hd,hld->hl', q[b], K_) / math.sqrt(D)
+        if mrows is not None:
+            s = s + mrows[b, None, :tb + 1]
+        out[b] = torch.einsum('hl,hld->hd', torch.softmax(s, -1), V_)
+    return out.to(qkv.dtype)
 
 
 @R.register_kernel('mmha_decode', 'hip', dtypes=_FLOATS)
-def _mmha_hip(qkv, cache, t, mask):
+def _mmha_hip(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0):
     B, _, H, D = qkv.shape
     L = cache.shape[3]
     t_dev = None
@@ -744,6 +785,17 @@ def _mmha_hip(qkv, cache, t, mask):
             (t_dev is not None or 0 <= t < L)):
         raise ValueError(f"mmha_decode: qkv {tuple(qkv.shape)} / cache {tuple(cache.shape)} / "
                          f"t={t} not supported by the HIP kernel")
+    if seq_lens is not None and not (seq_lens.is_cuda and seq_lens.dtype == torch.int32 and
+                                     seq_lens.is_contiguous() and seq_lens.numel() == B):
+        raise ValueError(f"mmha_decode: seq_lens must be a contiguous CUDA int32 [{B}] tensor")
+    if rotary is not None:
+        if not rotary_in_kernel(D, rotary_dims):
+            raise ValueError(f"mmha_decode: head_dim {D} with rotary_dims={rotary_dims} is not "
+                             "supported by the HIP kernel (half a chunk must be a multiple of 8)")
+        if not (rotary.is_cuda and rotary.dtype == torch.float32 and rotary.is_contiguous() and
+                tuple(rotary.shape) == (2, B, D)):
+            raise ValueError(f"mmha_decode: rotary must be a contiguous CUDA fp32 [2, {B}, {D}] tensor")
+        R._STATS[('mmha_decode_rotary', 'hip')] += 1
     splits = _native.lib().mmha_splits(B, H, L - 1 if t_dev is not None else t)
     ws = torch.empty(B * H * splits * (2 + D) + 4 if splits > 1 else 4, device=qkv.device,
                      dtype=torch.float32)
@@ -757,17 +809,55 @@ def _mmha_hip(qkv, cache, t, mask):
     _native.lib().mmha_decode(_ptr(qkv), _ptr(cache), _ptr(mask) if mask is not None else 0,
                               _ptr(ws), _ptr(out), B, H, L, D, int(t),
                               _ptr(t_dev) if t_dev is not None else 0, splits, mlen,
-                              1.0 / math.sqrt(D), _dt(qkv), _stream())
+                              1.0 / math.sqrt(D), _dt(qkv), _stream(),
+                              _ptr(seq_lens) if seq_lens is not None else 0,
+                              _ptr(rotary) if rotary is not None else 0, int(rotary_dims))
     return out
 
 
-def mmha_decode(qkv, cache, time_step, mask=None):
+def rotary_in_kernel(head_dim, rotary_dims):
+    """Whether the HIP decode kernel can apply the rotary embedding itself: a lane owns 8
+    contiguous dims, so half a rotary chunk has to be a whole number of lanes."""
+    return (head_dim in (64, 128, 256) and rotary_dims >= 1 and
+            head_dim % (16 * rotary_dims) == 0)
+
+
+def mmha_decode(qkv, cache, time_step, mask=None, seq_lens=None, rotary=None, rotary_dims=0):
     """One decode step of multi-head attention; returns [B, H, D] and appends K/V to
     ``cache`` at ``time_step`` in place. ``time_step`` may be a CUDA int32 tensor: the kernel
-    reads it on the device (no host sync), so the step can live in a captured HIP graph."""
+    reads it on the device (no host sync), so the step can live in a captured HIP graph.
+
+    ``seq_lens`` ([B]; list, numpy array or tensor) gives sequence ``b`` its own position
+    ``t_b = seq_lens[b]``: it reads cache positions [0, t_b) and appends at t_b, and
+    ``time_step`` is then the batch-wide upper bound. Host ``seq_lens`` with a host
+    ``time_step`` are validated here (0 <= t_b <= time_step < L); device values are not
+    synced — a sequence whose position is out of range gets a zero output and no write.
+    ``rotary`` ((cos, sin) or a stacked tensor, [2, B, D]) rotates q and the new k with the
+    half-split rule inside each of ``rotary_dims`` chunks of the head dim before attention."""
     if not isinstance(time_step, torch.Tensor):
         time_step = int(time_step)
-    return R.dispatch('mmha_decode', qkv, qkv.contiguous(), cache, time_step, mask)
+    if seq_lens is None and rotary is None:
+        return R.dispatch('mmha_decode', qkv, qkv.contiguous(), cache, time_step, mask)
+    B, D = qkv.shape[0], qkv.shape[-1]
+    if seq_lens is not None:
+        on_host = not (isinstance(seq_lens, torch.Tensor) and seq_lens.is_cuda)
+        seq_lens = torch.as_tensor(seq_lens).reshape(-1)
+        if seq_lens.numel() != B:
+            raise ValueError(f"mmha_decode: seq_lens has {seq_lens.numel()} entries for batch {B}")
+        if on_host and not (isinstance(time_step, torch.Tensor) and time_step.is_cuda):
+            ts, L = int(time_step), cache.shape[3]
+            if not all(0 <= int(n) <= ts < L for n in seq_lens.tolist()):
+                raise ValueError(f"mmha_decode: need 0 <= seq_lens <= time_step < {L}, got "
+                                 f"seq_lens={seq_lens.tolist()} time_step={ts}")
+        seq_lens = seq_lens.to(device=qkv.device, dtype=torch.int32).contiguous()
+    if rotary is not None:
+        if isinstance(rotary, (tuple, list)):
+            rotary = torch.stack([torch.as_tensor(r).reshape(B, D) for r in rotary])
+        if int(rotary_dims) < 1:
+            raise ValueError("mmha_decode: rotary needs rotary_dims >= 1")
+        rotary = rotary.reshape(2, B, D).to(device=qkv.device, dtype=torch.float32).contiguous()
+    return R.dispatch('mmha_decode', qkv, qkv.contiguous(), cache, time_step, mask,
+                      seq_lens=seq_lens, rotary=rotary, rotary_dims=int(rotary_dims))
 
 
 # =============================================================================

@@ -1,5 +1,6 @@
 """Decode-attention bandwidth: the HIP split-K kernel (K.mmha_decode) vs torch SDPA over
-the same KV cache, and end-to-end FusedMultiTransformer decode steps/s.
+the same KV cache, a ragged batch (per-sequence seq_lens) next to its padded-and-masked twin,
+and end-to-end FusedMultiTransformer decode steps/s.
 
 usage: python scripts/decode_bench.py [--quick]"""
 import argparse
@@ -48,6 +49,24 @@ def main():
                          sdpa_us=round(ref * 1e6, 1), hip_TBps=round(gb / hip / 1e3, 2),
                          sdpa_TBps=round(gb / ref / 1e3, 2), splits=K._native.lib().mmha_splits(B, H, t)))
         print(json.dumps(rows[-1]), flush=True)
+    # ragged batch: every sequence at its own length (seq_lens), next to the same batch run
+    # the only way possible without it — all sequences at 4095 behind an additive mask.
+    # TB/s counts the bytes actually valid, sum(len_b + 1) K and V rows, for both.
+    B, H, D, t = 8, 32, 128, 4095
+    lens = [int(round(512 + i * (4095 - 512) / (B - 1))) for i in range(B)]
+    qkv = torch.randn(B, 3, H, D, device='cuda', dtype=torch.bfloat16)
+    cache = torch.randn(2, B, H, t + 1, D, device='cuda', dtype=torch.bfloat16)
+    sl = torch.tensor(lens, dtype=torch.int32, device='cuda')
+    mask = torch.zeros(B, t + 1, device='cuda')
+    for b, n in enumerate(lens):
+        mask[b, n:t] = float('-inf')
+    ragged = bench(lambda: K.mmha_decode(qkv, cache, t, seq_lens=sl))
+    masked = bench(lambda: K.mmha_decode(qkv, cache, t, mask))
+    gb = 2 * H * sum(n + 1 for n in lens) * D * 2 / 1e9
+    print(json.dumps(dict(B=B, H=H, D=D, lens=lens, ragged_us=round(ragged * 1e6, 1),
+                          masked_us=round(masked * 1e6, 1), valid_GB=round(gb, 4),
+                          ragged_TBps=round(gb / ragged / 1e3, 2),
+                          masked_TBps=round(gb / masked / 1e3, 2))), flush=True)
     # end-to-end decode: 24-layer 2048-wide model (GPT-3 1.3B shape), batch 8
     import paddle_ray_amd as paddle
     from paddle_ray_amd.incubate.nn import FusedMultiTransformer
