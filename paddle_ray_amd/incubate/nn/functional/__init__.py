@@ -191,6 +191,21 @@ def _qkv(y, w, b, trans_qkvw):
     return out.view(B, S, 3, H, D)
 
 
+def _qkv_rows(y, w, b, trans_qkvw):
+    """Grouped-query projection: w [N, D, E] (or [E, N, D]) with N = H + 2*KVH head rows, the
+    query heads first, then the k heads, then the v heads. Returns [B, S, N, D]."""
+    B, S, E = y.shape
+    if trans_qkvw:
+        N, D, _ = w.shape
+        out = K.linear_nt(y.reshape(B * S, E), w.reshape(N * D, E))
+    else:
+        _, N, D = w.shape
+        out = K.linear(y.reshape(B * S, E), w.reshape(E, N * D))
+    if b is not None:
+        out = out + b.reshape(-1).to(out.dtype)
+    return out.view(B, S, N, D)
+
+
 def _ones_zeros(t, n, like):
     return t if t is not None else (torch.ones(n, dtype=like.dtype, device=like.device) if n
                                      else None)
@@ -202,7 +217,7 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
                             cache_kvs=None, pre_caches=None, seq_lens=None, rotary_embs=None,
                             time_step=None, attn_mask=None, dropout_rate=0.0, rotary_emb_dims=0,
                             activation="gelu", training=False, mode='upscale_in_train',
-                            trans_qkvw=True, ring_id=-1, name=None):
+                            trans_qkvw=True, ring_id=-1, name=None, gqa_group_size=-1):
     """N transformer layers for inference / generation (parity: reference
     incubate/nn/functional/fused_transformer.py:872 and fused_multi_transformer_op.cu.h).
 
@@ -217,6 +232,13 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
       ``time_step`` stays the phase switch and the batch-wide upper bound (max of seq_lens).
       ``rotary_embs`` ([2, B, 1, 1, D], each sequence's own position) is applied inside the
       kernel when the head dim allows it, else by the torch rotation before it.
+    * grouped-query attention (``gqa_group_size`` = KVH > 0, the number of K/V heads): qkv
+      weights are [H + 2*KVH, D, E] ([E, H + 2*KVH, D] with ``trans_qkvw=False``), biases
+      [H + 2*KVH, D] — the query heads, then the k heads, then the v heads — and
+      ``cache_kvs`` / ``pre_caches`` hold KVH heads ([2, B, KVH, ., D]). Query head ``h`` reads
+      K/V head ``h // (H // KVH)``. The decode phase hands the row to the grouped-query HIP
+      kernel, which streams every cached K/V row once for its H / KVH query heads; the context
+      phase expands K/V over heads for the flash / SDPA call and caches the KVH heads.
     * every residual add + dropout + following LayerNorm is ONE add_dropout_layer_norm
       kernel; FFN1 runs with its bias+activation in the GEMM epilogue.
     Returns ``out`` or ``(out, cache_kvs)`` when caches are given (updated in place)."""
@@ -227,6 +249,7 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
     n = len(qkv_weights)
     p = dropout_rate if training else 0.0
     decode = time_step is not None
+    KVH = int(gqa_group_size) if gqa_group_size is not None and int(gqa_group_size) > 0 else 0
     if decode and not isinstance(time_step, int):
         ts = _u(time_step)
         # a device int32 step stays on the device (graph-capturable decode); host -> int
@@ -254,13 +277,28 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
     y = K.layer_norm(h, lnp(ln_scales, 0, one_w), lnp(ln_biases, 0, zero_b), epsilon) \
         if pre_layer_norm else h
     for i in range(n):
-        qkv = _qkv(y, _u(qkv_weights[i]), _t(qkv_biases[i]) if qkv_biases else None, trans_qkvw)
-        H, D = qkv.shape[3], qkv.shape[4]
-        if rot is not None:
-            q = _rotary(qkv[:, :, 0], rot[0], rot[1], rotary_emb_dims)
-            k = _rotary(qkv[:, :, 1], rot[0], rot[1], rotary_emb_dims)
-            qkv = torch.stack([q, k, qkv[:, :, 2]], 2)
+        qb = _t(qkv_biases[i]) if qkv_biases else None
+        if KVH:
+            qkv = _qkv_rows(y, _u(qkv_weights[i]), qb, trans_qkvw)   # [B, S, H + 2*KVH, D]
+            H, D = qkv.shape[2] - 2 * KVH, qkv.shape[3]
+            if H <= 0 or H % KVH != 0:
+                raise ValueError(f"fused_multi_transformer: qkv weight {i} has {qkv.shape[2]} head "
+                                 f"rows, which is not H + 2*{KVH} with H a multiple of "
+                                 f"gqa_group_size={KVH}")
+            if rot is not None:                      # q and k heads; the v heads stay
+                qk = _rotary(qkv[:, :, :H + KVH], rot[0], rot[1], rotary_emb_dims)
+                qkv = torch.cat([qk, qkv[:, :, H + KVH:]], 2)
+        else:
+            qkv = _qkv(y, _u(qkv_weights[i]), qb, trans_qkvw)
+            H, D = qkv.shape[3], qkv.shape[4]
+            if rot is not None:
+                q = _rotary(qkv[:, :, 0], rot[0], rot[1], rotary_emb_dims)
+                k = _rotary(qkv[:, :, 1], rot[0], rot[1], rotary_emb_dims)
+                qkv = torch.stack([q, k, qkv[:, :, 2]], 2)
         cache = _u(cache_kvs[i]) if cache_kvs is not None else None
+        if KVH and cache is not None and (cache.dim() != 5 or cache.shape[2] != KVH):
+            raise ValueError(f"fused_multi_transformer: cache {i} is {tuple(cache.shape)}, "
+                             f"gqa_group_size={KVH} needs [2, B, {KVH}, max_len, D]")
         if decode:
             if cache is None:
                 raise ValueError("fused_multi_transformer: time_step needs cache_kvs")
@@ -268,7 +306,10 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
                               rotary_dims=rotary_emb_dims if krot is not None else 0
                               ).reshape(B, 1, H * D)
         else:
-            q, k, v = qkv.unbind(2)                  # [B, S, H, D]
+            if KVH:
+                q, k, v = qkv[:, :, :H], qkv[:, :, H:H + KVH], qkv[:, :, H + KVH:]
+            else:
+                q, k, v = qkv.unbind(2)              # [B, S, H, D]
             P = 0
             if pre_caches is not None and pre_caches[i] is not None:
                 pc = _u(pre_caches[i])               # [2, B, H, P, D]
@@ -278,6 +319,8 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
             if cache is not None:
                 cache[0, :, :, :P + S] = k.transpose(1, 2)
                 cache[1, :, :, :P + S] = v.transpose(1, 2)
+            if KVH and H != KVH:                     # the cache keeps KVH heads; attention sees H
+                k, v = k.repeat_interleave(H // KVH, 2), v.repeat_interleave(H // KVH, 2)
             if mask is None and sl is None and h.is_cuda and h.dtype in (torch.bfloat16,
                                                                          torch.float16):
                 o = K.flash_attention(q.contiguous(), k.contiguous(), v.contiguous(), causal=False)

@@ -135,7 +135,11 @@ class FusedMultiTransformer(Layer):
     FusedMultiTransformer): qkv [3, H, D, E], linear [E, E], ffn1 [E, F], ffn2 [F, E].
     ``forward(src, attn_mask, caches, ..., time_step)`` runs the context phase (caches
     filled in place) or, with ``time_step``, one decode step on the HIP cache kernel; there
-    ``seq_lens`` ([B], cache positions already filled per sequence) makes the batch ragged."""
+    ``seq_lens`` ([B], cache positions already filled per sequence) makes the batch ragged.
+    ``gqa_group_size`` = KVH > 0 is grouped-query attention with KVH K/V heads
+    (``self.kv_num_heads``), each shared by ``num_heads / KVH`` query heads: qkv is
+    [H + 2*KVH, D, E] (query heads, k heads, v heads), its bias [H + 2*KVH, D], and the caches
+    are [2, B, KVH, max_len, D]."""
 
     def __init__(self, embed_dim, num_heads, dim_feedforward, dropout_rate=0.0, activation="gelu",
                  normalize_before=True, ln_scale_attrs=None, ln_bias_attrs=None,
@@ -143,13 +147,19 @@ class FusedMultiTransformer(Layer):
                  linear_bias_attrs=None, ffn_ln_scale_attrs=None, ffn_ln_bias_attrs=None,
                  ffn1_weight_attrs=None, ffn1_bias_attrs=None, ffn2_weight_attrs=None,
                  ffn2_bias_attrs=None, epsilon=1e-5, num_layers=-1, nranks=1,
-                 trans_qkvw=True, ring_id=-1, name=None):
+                 trans_qkvw=True, ring_id=-1, name=None, gqa_group_size=-1):
         super().__init__()
         if num_layers < 0:
             num_layers = len(qkv_weight_attrs) if isinstance(qkv_weight_attrs, (list, tuple)) else 1
         assert embed_dim % num_heads == 0
         self.embed_dim, self.num_heads = embed_dim, num_heads
         self.head_dim = embed_dim // num_heads
+        # grouped-query attention: gqa_group_size K/V heads, each shared by num_heads / it query heads
+        self._gqa_group_size = int(gqa_group_size) if gqa_group_size and int(gqa_group_size) > 0 else -1
+        self.kv_num_heads = self._gqa_group_size if self._gqa_group_size > 0 else num_heads
+        if num_heads % self.kv_num_heads != 0:
+            raise ValueError(f"FusedMultiTransformer: num_heads={num_heads} is not a multiple of "
+                             f"gqa_group_size={gqa_group_size}")
         self.normalize_before, self._epsilon = normalize_before, epsilon
         self.dropout_rate, self.activation, self._trans_qkvw = dropout_rate, activation, trans_qkvw
         one = I.Constant(1.0)
@@ -163,12 +173,17 @@ class FusedMultiTransformer(Layer):
             setattr(self, n, [])
         E, H, D, F = embed_dim, num_heads, self.head_dim, dim_feedforward
         qkv_shape = [3, H, D, E] if trans_qkvw else [E, 3, H, D]
+        qkv_bias_shape = [3, H, D]
+        if self._gqa_group_size > 0:     # head rows: H query heads, then the k heads, then the v heads
+            N = H + 2 * self.kv_num_heads
+            qkv_shape = [N, D, E] if trans_qkvw else [E, N, D]
+            qkv_bias_shape = [N, D]
         for i in range(num_layers):
             specs = (
                 ('ln_scales', [E], ln_scale_attrs, False, one),
                 ('ln_biases', [E], ln_bias_attrs, True, None),
                 ('qkv_weights', qkv_shape, qkv_weight_attrs, False, None),
-                ('qkv_biases', [3, H, D], qkv_bias_attrs, True, None),
+                ('qkv_biases', qkv_bias_shape, qkv_bias_attrs, True, None),
                 ('linear_weights', [E, E], linear_weight_attrs, False, None),
                 ('linear_biases', [E], linear_bias_attrs, True, None),
                 ('ffn_ln_scales', [E], ffn_ln_scale_attrs, False, one),
@@ -192,7 +207,7 @@ class FusedMultiTransformer(Layer):
             pre_caches=pre_caches, seq_lens=seq_lens, rotary_embs=rotary_embs,
             time_step=time_step, attn_mask=attn_mask, dropout_rate=self.dropout_rate,
             rotary_emb_dims=rotary_emb_dims, activation=self.activation, training=self.training,
-            trans_qkvw=self._trans_qkvw)
+            trans_qkvw=self._trans_qkvw, gqa_group_size=self._gqa_group_size)
 
 
 class FusedMultiTransformerDecoder:
@@ -221,9 +236,10 @@ class FusedMultiTransformerDecoder:
         self.B, self.L = int(batch_size), int(max_seq_len)
         p0 = model.qkv_weights[0]._t
         self.dev, self.dtype = p0.device, p0.dtype
-        H, D, E = model.num_heads, model.head_dim, model.embed_dim
+        D, E = model.head_dim, model.embed_dim
+        KVH = getattr(model, 'kv_num_heads', model.num_heads)    # grouped-query models cache KVH heads
         n = len(model.qkv_weights)
-        self.caches = [torch.zeros(2, self.B, H, self.L, D, device=self.dev, dtype=self.dtype)
+        self.caches = [torch.zeros(2, self.B, KVH, self.L, D, device=self.dev, dtype=self.dtype)
                        for _ in range(n)]
         self.t = torch.zeros(1, dtype=torch.int32, device=self.dev)
         self.lens = torch.zeros(self.B, dtype=torch.int32, device=self.dev)

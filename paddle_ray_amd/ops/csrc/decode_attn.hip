@@ -310,4 +310,25 @@ int pra_mmha_decode(const void* qkv, void* cache, const float* mask, float* ws, 
 #undef PRA_MMHA
   return -1;
 }
+
+// the split merge alone, for split-K kernels in other files that fill the same workspace layout
+// (decode_attn_gqa.hip): ws_ml [B, H, splits, 2], ws_acc [B, H, splits, D] -> out [B, H, D]
+int pra_mmha_combine(const float* ws_ml, const float* ws_acc, void* out, int B, int H, int D, int splits, int dt,
+                     hipStream_t s) {
+#define PRA_COMBINE(TT)                                                                                      \
+  switch (D) {                                                                                               \
+    case 64: hipLaunchKernelGGL((mmha_combine_k<TT, 64>), dim3(H, B), dim3(64), 0, s, ws_ml, ws_acc, (TT*)out, \
+                                splits); return 0;                                                           \
+    case 128: hipLaunchKernelGGL((mmha_combine_k<TT, 128>), dim3(H, B), dim3(128), 0, s, ws_ml, ws_acc,       \
+                                 (TT*)out, splits); return 0;                                                \
+    case 256: hipLaunchKernelGGL((mmha_combine_k<TT, 256>), dim3(H, B), dim3(256), 0, s, ws_ml, ws_acc,       \
+                                 (TT*)out, splits); return 0;                                                \
+    default: return -1;                                                                                      \
+  }
+  if (dt == kBF16) { PRA_COMBINE(bf16) }
+  if (dt == kF16) { PRA_COMBINE(f16) }
+  if (dt == kF32) { PRA_COMBINE(float) }
+#undef PRA_COMBINE
+  return -1;
+}
 }

@@ -1,0 +1,328 @@
+// Grouped-query decode attention over a KV cache, for gfx950: KVH < H K/V heads, each shared by
+// R = H / KVH consecutive query heads (query head h reads K/V head h / R).
+//
+// Parity: the reference's masked multihead attention decoder kernel behind
+// fused_multi_transformer with gqa_group_size = KVH (qkv row [H + 2*KVH, D]: the query heads,
+// then KVH k heads, then KVH v heads; cache [2, B, KVH, L, D]).
+//
+// Same streaming scheme as decode_attn.hip (split-K, G = D/8 lanes per key, 16-byte coalesced
+// loads, two keys per lane group in flight), with one change that is the point of GQA on a
+// memory-bound step: the grid is (splits, KVH, B), so every K and V row is loaded ONCE and
+// scored against all R query rows of its K/V head. Each lane group keeps R scaled q rows and R
+// online-softmax states (m, l, acc[8]) in registers; the two keys of an iteration share one
+// rescale of each state. Key groups merge by xor-shuffle, waves through LDS, and lane group r
+// of the workgroup finishes query head r. The R partials land in the workspace of the plain
+// kernel, indexed by query head ((b*H + h)*splits + split), so mmha_combine_k merges them
+// unchanged on grid (H, B).
+//
+// seq_lens / rot / mask / t_dev are runtime null checks in the one instantiation per
+// (T, D, R); their semantics are those of decode_attn.hip: a key range past t_b leaves with
+// the empty partial, a guarded sequence gets zeros and no write, rot rotates the R q rows and
+// the one new k row in registers, the rotated k is rounded once and that value is both
+// cached and scored. The workgroup that owns t_b appends the K/V row of its K/V head.
+#include "common.h"
+
+extern "C" int pra_mmha_combine(const float* ws_ml, const float* ws_acc, void* out, int B, int H, int D,
+                                int splits, int dt, hipStream_t s);
+
+namespace pra {
+namespace {
+
+constexpr int kWaves = 4;
+
+typedef float f2 __attribute__((ext_vector_type(2)));
+
+// v + (v of the lane that the DPP control selects): the cross-lane operand rides on the add
+// itself, so the R reductions per key cost VALU slots only and no LDS-pipe round trips
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v) {
+  return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+
+// sum over the G (8, 16 or 32) consecutive lanes of a key group, the same bits in every lane:
+// the two quad swaps, then the mirror inside each 8 and inside each 16 lanes
+template <int G>
+__device__ __forceinline__ float group_sum(float v) {
+  static_assert(G == 8 || G == 16 || G == 32, "key groups of 8, 16 or 32 lanes");
+  v = dpp_add<0xB1>(v);   // quad_perm [1, 0, 3, 2]
+  v = dpp_add<0x4E>(v);   // quad_perm [2, 3, 0, 1]
+  v = dpp_add<0x141>(v);  // row_half_mirror
+  if constexpr (G >= 16) v = dpp_add<0x140>(v);  // row_mirror
+  if constexpr (G == 32) v += __shfl_xor(v, 16, 64);
+  return v;
+}
+
+// merge (m2, l2, a2) into (m, l, a)
+__device__ __forceinline__ void merge8(float& m, float& l, float* a, float m2, float l2, const float* a2) {
+  const float M = fmaxf(m, m2);
+  if (M == -INFINITY) return;
+  const float c1 = (m == -INFINITY) ? 0.f : __expf(m - M);
+  const float c2 = (m2 == -INFINITY) ? 0.f : __expf(m2 - M);
+  l = l * c1 + l2 * c2;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) a[i] = a[i] * c1 + a2[i] * c2;
+  m = M;
+}
+
+// x[8] (dims d0.. of one head row) rotated against its partner half a chunk away; c / s are
+// the lane's 8 cos / sin values, shared by every row the lane rotates
+template <typename T>
+__device__ __forceinline__ void rotate8(const T* row, int d0, int half, bool left, const float* c, const float* s,
+                                        float* x) {
+  float p[8];
+  load8<T>(row + (left ? d0 + half : d0 - half), p);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) x[i] = left ? x[i] * c[i] - p[i] * s[i] : x[i] * c[i] + p[i] * s[i];
+}
+
+template <typename T, int D, int R>
+__global__ void __launch_bounds__(kWaves * 64) mmha_gqa_split_k(
+    const T* __restrict__ qkv,      // [B, H + 2*KVH, D] (bias already added)
+    T* __restrict__ cache,          // [2, B, KVH, L, D]
+    const float* __restrict__ mask, // [B, mask_len] additive, or null
+    float* __restrict__ ws_ml,      // [B, H, S, 2]
+    float* __restrict__ ws_acc,     // [B, H, S, D]
+    T* __restrict__ out,            // [B, H, D] (used when splits == 1)
+    int B, int KVH, int L, int t_host, const int* __restrict__ t_dev, int keys_per_split, int mask_len,
+    float scale,
+    const int* __restrict__ seq_lens,  // [B] per-sequence position, or null
+    const float* __restrict__ rot,     // [2, B, D] cos then sin, or null
+    int rot_dims) {
+  int t = t_dev ? t_dev[0] : t_host;
+  constexpr int G = D / 8;            // lanes per key
+  constexpr int KPW = 64 / G;         // keys per wave per sub-step
+  static_assert(kWaves * KPW >= R, "one lane group per query head in the epilogue");
+  const int split = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z;
+  const int splits = gridDim.x;
+  const int H = KVH * R, h0 = kvh * R;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int gl = lane % G, grp = lane / G;
+  bool in_bound = true;
+  if (seq_lens) {  // this sequence's own position; t_host / t_dev stay the bound that sized the grid
+    t = seq_lens[b];
+    in_bound = t_dev || t <= t_host;
+  }
+  const bool t_ok = in_bound && t >= 0 && t < L && !(mask && mask_len < t + 1);
+  const int lo = split * keys_per_split;
+  const int hi = t_ok ? min(t + 1, lo + keys_per_split) : lo;
+
+  const size_t rows = (size_t)H + 2 * KVH;
+  const T* qrow = qkv + ((size_t)b * rows + h0) * D;          // R consecutive query rows
+  const T* knew = qkv + ((size_t)b * rows + H + kvh) * D;
+  const T* vnew = knew + (size_t)KVH * D;
+  T* kc = cache + ((size_t)b * KVH + kvh) * (size_t)L * D;
+  T* vc = cache + (((size_t)B + b) * KVH + kvh) * (size_t)L * D;
+  const size_t w0 = ((size_t)b * H + h0) * splits + split;    // partial of query head h0; head r: + r*splits
+
+  if (hi <= lo) {  // a key range past t_b, or a guarded position: no loads, R empty partials
+    if (splits == 1) {
+      if (wave == 0 && grp == 0) {
+        const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int r = 0; r < R; ++r) store8<T>(out + ((size_t)b * H + h0 + r) * D + gl * 8, z);
+      }
+    } else if (threadIdx.x < R) {
+      *reinterpret_cast<float2*>(ws_ml + (w0 + (size_t)threadIdx.x * splits) * 2) = make_float2(-INFINITY, 0.f);
+    }
+    return;
+  }
+
+  float q[R][8];
+  float kt[8];  // the token's own k exactly as the cache holds it
+#pragma unroll
+  for (int r = 0; r < R; ++r) load8<T>(qrow + r * D + gl * 8, q[r]);
+  load8<T>(knew + gl * 8, kt);
+  if (rot) {
+    const int chunk = D / rot_dims, half = chunk >> 1;
+    const bool left = ((gl * 8) % chunk) < half;
+    float c[8], s[8];
+    load8<float>(rot + (size_t)b * D + gl * 8, c);
+    load8<float>(rot + ((size_t)B + b) * D + gl * 8, s);
+#pragma unroll
+    for (int r = 0; r < R; ++r) rotate8<T>(qrow + r * D, gl * 8, half, left, c, s, q[r]);
+    rotate8<T>(knew, gl * 8, half, left, c, s, kt);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) kt[i] = Cvt<T>::to(Cvt<T>::from(kt[i]));  // rounded once
+  }
+  if (t < hi && wave == 0 && grp == 0) {  // append the new token (hi > lo here, so t_ok and t >= lo)
+    float v[8];
+    store8<T>(kc + (size_t)t * D + gl * 8, kt);
+    load8<T>(vnew + gl * 8, v);
+    store8<T>(vc + (size_t)t * D + gl * 8, v);
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) q[r][i] *= scale;
+  }
+
+  float m[R], l[R], acc[R][8];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    m[r] = -INFINITY;
+    l[r] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[r][i] = 0.f;
+  }
+
+  const float* mrow = mask ? mask + (size_t)b * mask_len : nullptr;
+  constexpr int STEP = kWaves * KPW * 2;
+  for (int base = lo; base < hi; base += STEP) {
+    float kx[2][8], vx[2][8], add[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int key = base + (u * kWaves + wave) * KPW + grp;
+      const int kk = key < hi ? key : lo;
+      const T* kp = (kk == t) ? knew : kc + (size_t)kk * D;
+      const T* vp = (kk == t) ? vnew : vc + (size_t)kk * D;
+      load8<T>(kp + gl * 8, kx[u]);
+      load8<T>(vp + gl * 8, vx[u]);
+      if (kk == t) {  // the token's own key: the (rotated, rounded) registers, not the raw row
+#pragma unroll
+        for (int i = 0; i < 8; ++i) kx[u][i] = kt[i];
+      }
+      // a key past the range scores -inf: its weight is exactly 0
+      add[u] = key < hi ? (mrow ? mrow[key] : 0.f) : -INFINITY;
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      f2 d0 = {0.f, 0.f}, d1 = {0.f, 0.f};  // packed fp32 FMAs: even and odd dims apart
+#pragma unroll
+      for (int i = 0; i < 8; i += 2) {
+        const f2 qq = {q[r][i], q[r][i + 1]};
+        d0 += qq * f2{kx[0][i], kx[0][i + 1]};
+        d1 += qq * f2{kx[1][i], kx[1][i + 1]};
+      }
+      float s0 = d0.x + d0.y, s1 = d1.x + d1.y;
+      s0 = group_sum<G>(s0) + add[0];
+      s1 = group_sum<G>(s1) + add[1];
+      const float mn = fmaxf(m[r], fmaxf(s0, s1));
+      const float ms = (mn == -INFINITY) ? 0.f : mn;  // fully masked so far: every weight below is 0
+      const float c = __expf(m[r] - ms);
+      const float p0 = __expf(s0 - ms), p1 = __expf(s1 - ms);
+      l[r] = l[r] * c + p0 + p1;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc[r][i] = acc[r][i] * c + p0 * vx[0][i] + p1 * vx[1][i];
+      m[r] = mn;
+    }
+  }
+
+  // merge the KPW key groups of this wave (lanes gl, gl+G, ...)
+#pragma unroll
+  for (int o = G; o < 64; o <<= 1) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const float m2 = __shfl_xor(m[r], o, 64), l2 = __shfl_xor(l[r], o, 64);
+      float a2[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) a2[i] = __shfl_xor(acc[r][i], o, 64);
+      merge8(m[r], l[r], acc[r], m2, l2, a2);
+    }
+  }
+  // merge the waves through LDS: every wave posts its R states, lane group r finishes head r
+  __shared__ float s_ml[kWaves][R][2];
+  __shared__ __attribute__((aligned(16))) float s_acc[kWaves][R][D];
+  if (grp == 0) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      *reinterpret_cast<float4*>(&s_acc[wave][r][gl * 8]) = make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
+      *reinterpret_cast<float4*>(&s_acc[wave][r][gl * 8 + 4]) =
+          make_float4(acc[r][4], acc[r][5], acc[r][6], acc[r][7]);
+      if (gl == 0) { s_ml[wave][r][0] = m[r]; s_ml[wave][r][1] = l[r]; }
+    }
+  }
+  __syncthreads();
+  const int r = wave * KPW + grp;  // this lane group's query head
+  if (r >= R) return;
+  float fm = s_ml[0][r][0], fl = s_ml[0][r][1], fa[8];
+  load8<float>(&s_acc[0][r][gl * 8], fa);
+  for (int w = 1; w < kWaves; ++w) {
+    float a2[8];
+    load8<float>(&s_acc[w][r][gl * 8], a2);
+    merge8(fm, fl, fa, s_ml[w][r][0], s_ml[w][r][1], a2);
+  }
+  if (splits == 1) {
+    const float inv = fl > 0.f ? 1.f / fl : 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) fa[i] *= inv;
+    store8<T>(out + ((size_t)b * H + h0 + r) * D + gl * 8, fa);
+    return;
+  }
+  const size_t w = w0 + (size_t)r * splits;
+  store8<float>(ws_acc + w * D + gl * 8, fa);
+  if (gl == 0) *reinterpret_cast<float2*>(ws_ml + w * 2) = make_float2(fm, fl);
+}
+
+struct Args {
+  const void* qkv;
+  void* cache;
+  const float* mask;
+  float* ws;
+  void* out;
+  int B, H, KVH, L, t;
+  const int* t_dev;
+  int splits, mask_len;
+  float scale;
+  int dt;
+  const int* seq_lens;
+  const float* rot;
+  int rot_dims;
+  hipStream_t s;
+};
+
+template <typename T, int D, int R>
+int launch(const Args& a) {
+  const int keys = a.t_dev ? a.L : a.t + 1;  // device position: splits cover the whole cache
+  const int per = (keys + a.splits - 1) / a.splits;
+  float* ws_ml = a.ws;
+  float* ws_acc = a.ws + (((size_t)a.B * a.H * a.splits * 2 + 3) / 4) * 4;  // 16-B aligned, as the plain kernel
+  hipLaunchKernelGGL((mmha_gqa_split_k<T, D, R>), dim3(a.splits, a.KVH, a.B), dim3(kWaves * 64), 0, a.s,
+                     (const T*)a.qkv, (T*)a.cache, a.mask, ws_ml, ws_acc, (T*)a.out, a.B, a.KVH, a.L, a.t, a.t_dev,
+                     per, a.mask_len, a.scale, a.seq_lens, a.rot, a.rot_dims);
+  if (a.splits > 1) return pra_mmha_combine(ws_ml, ws_acc, a.out, a.B, a.H, D, a.splits, a.dt, a.s);
+  return 0;
+}
+
+template <typename T, int D>
+int launch_r(const Args& a) {
+  switch (a.H / a.KVH) {
+    case 2: return launch<T, D, 2>(a);
+    case 4: return launch<T, D, 4>(a);
+    case 8: return launch<T, D, 8>(a);
+    default: return -1;
+  }
+}
+
+template <typename T>
+int launch_d(int D, const Args& a) {
+  switch (D) {
+    case 64: return launch_r<T, 64>(a);
+    case 128: return launch_r<T, 128>(a);
+    case 256: return launch_r<T, 256>(a);
+    default: return -1;
+  }
+}
+
+}  // namespace
+}  // namespace pra
+
+using namespace pra;
+
+extern "C" {
+// qkv [B, H + 2*KVH, D], cache [2, B, KVH, L, D], R = H / KVH in {2, 4, 8}. splits come from
+// pra_mmha_splits(B, KVH, t) (the workgroup count is B*KVH*splits); ws is the plain kernel's
+// workspace, B*H*splits*(2 + D) + 4 floats. Everything else as pra_mmha_decode.
+int pra_mmha_gqa_decode(const void* qkv, void* cache, const float* mask, float* ws, void* out, int B, int H, int KVH,
+                        int L, int D, int t, const int* t_dev, int splits, int mask_len, float scale, int dt,
+                        const int* seq_lens, const float* rot, int rot_dims, hipStream_t s) {
+  if (splits < 1 || B < 1 || B > 65535 || KVH < 1 || KVH > 65535 || H <= KVH || H % KVH != 0 || L < 1) return -1;
+  if (!t_dev && (t < 0 || t >= L || (mask && mask_len < t + 1))) return -1;
+  if (rot && (rot_dims < 1 || D % (16 * rot_dims) != 0)) return -1;  // a half chunk is whole 8-dim lanes
+  const Args a{qkv, cache, mask, ws, out, B, H, KVH, L, t, t_dev, splits, mask_len, scale, dt, seq_lens, rot,
+               rot_dims, s};
+  if (dt == kBF16) return launch_d<bf16>(D, a);
+  if (dt == kF16) return launch_d<f16>(D, a);
+  if (dt == kF32) return launch_d<float>(D, a);
+  return -1;
+}
+}

@@ -717,6 +717,8 @@ def vocab_parallel_cross_entropy(logits, labels, pg=None, world=1, rank=0, ignor
 # Ragged batches: seq_lens [B] gives every sequence its own t_b (t stays the batch-wide upper
 # bound), rotary [2, B, D] (cos, sin) rotates q and the new k before anything else. A
 # sequence whose position is out of range gets a zero output and no cache write.
+# Grouped-query attention (decode_attn_gqa.hip): a 3-D qkv [B, H + 2*KVH, D] (query heads, then
+# k heads, then v heads) over a cache [2, B, KVH, L, D]; query head h reads K/V head h // (H/KVH).
 # =============================================================================
 def _rotate_rows(x, cos, sin, dims):
     """Half-split rotation inside each of ``dims`` chunks: x [B, H, D] fp32, cos/sin [B, D]."""
@@ -738,7 +740,7 @@ def _mmha_ref(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0):
         t = int(t.reshape(-1)[0])
     else:
         bound = t
-    if seq_lens is None and rotary is None:
+    if seq_lens is None and rotary is None and qkv.dim() == 4:
         q, k, v = qkv.unbind(1)                                   # [B, H, D]
         cache[0, :, :, t] = k
         cache[1, :, :, t] = v
@@ -748,8 +750,15 @@ def _mmha_ref(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0):
             s = s + mask.reshape(mask.shape[0], -1)[:, None, :t + 1].float()
         p = torch.softmax(s, -1)
         return torch.einsum('bhl,bhld->bhd', p, V_).to(qkv.dtype)
-    B, _, H, D = qkv.shape
-    q, k, v = qkv[:, 0].float(), qkv[:, 1].float(), qkv[:, 2]
+    if qkv.dim() == 3:                                            # grouped-query row [B, H + 2*KVH, D]
+        R._STATS[('mmha_decode_gqa', 'ref')] += 1
+        B, D, KVH = qkv.shape[0], qkv.shape[2], cache.shape[2]
+        H = qkv.shape[1] - 2 * KVH
+        q, k, v = qkv[:, :H].float(), qkv[:, H:H + KVH].float(), qkv[:, H + KVH:]
+    else:
+        B, _, H, D = qkv.shape
+        q, k, v = qkv[:, 0].float(), qkv[:, 1].float(), qkv[:, 2]
+    rep = H // k.shape[1]                                         # query heads per K/V head
     if rotary is not None:
         R._STATS[('mmha_decode_rotary', 'ref')] += 1
         cos, sin = rotary.reshape(2, B, D).float().to(qkv.device)
@@ -764,6 +773,8 @@ def _mmha_ref(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0):
         cache[0, b, :, tb] = k[b]
         cache[1, b, :, tb] = v[b]
         K_, V_ = cache[0, b, :, :tb + 1].float(), cache[1, b, :, :tb + 1].float()
+        if rep > 1:                                               # query head h reads K/V head h // rep
+            K_, V_ = K_.repeat_interleave(rep, 0), V_.repeat_interleave(rep, 0)
         s = torch.einsum('hd,hld->hl', q[b], K_) / math.sqrt(D)
         if mrows is not None:
             s = s + mrows[b, None, :tb + 1]
@@ -773,7 +784,16 @@ def _mmha_ref(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0):
 
 @R.register_kernel('mmha_decode', 'hip', dtypes=_FLOATS)
 def _mmha_hip(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0):
-    B, _, H, D = qkv.shape
+    gqa = qkv.dim() == 3            # [B, H + 2*KVH, D]: the grouped-query kernel (decode_attn_gqa.hip)
+    if gqa:
+        B, D, KVH = qkv.shape[0], qkv.shape[2], cache.shape[2]
+        H = qkv.shape[1] - 2 * KVH
+        if H // KVH not in GQA_RATIOS:
+            raise ValueError(f"mmha_decode: {H} query heads over {KVH} K/V heads is a ratio of "
+                             f"{H // KVH}; the HIP kernel supports {GQA_RATIOS}")
+    else:
+        B, _, H, D = qkv.shape
+        KVH = H
     L = cache.shape[3]
     t_dev = None
     if isinstance(t, torch.Tensor):  # device position (HIP-graph decode loops): read in-kernel
@@ -781,7 +801,7 @@ def _mmha_hip(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0):
             raise ValueError("mmha_decode: a tensor time_step must be a CUDA int32 tensor")
         t_dev, t = t, 0
     if not (qkv.is_contiguous() and cache.is_contiguous() and cache.dtype == qkv.dtype and
-            tuple(cache.shape) == (2, B, H, L, D) and D in (64, 128, 256) and
+            tuple(cache.shape) == (2, B, KVH, L, D) and D in (64, 128, 256) and
             (t_dev is not None or 0 <= t < L)):
         raise ValueError(f"mmha_decode: qkv {tuple(qkv.shape)} / cache {tuple(cache.shape)} / "
                          f"t={t} not supported by the HIP kernel")
@@ -796,7 +816,8 @@ def _mmha_hip(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0):
                 tuple(rotary.shape) == (2, B, D)):
             raise ValueError(f"mmha_decode: rotary must be a contiguous CUDA fp32 [2, {B}, {D}] tensor")
         R._STATS[('mmha_decode_rotary', 'hip')] += 1
-    splits = _native.lib().mmha_splits(B, H, L - 1 if t_dev is not None else t)
+    # the workgroup count sizes the splits: one workgroup per key range and K/V head
+    splits = _native.lib().mmha_splits(B, KVH, L - 1 if t_dev is not None else t)
     ws = torch.empty(B * H * splits * (2 + D) + 4 if splits > 1 else 4, device=qkv.device,
                      dtype=torch.float32)
     out = torch.empty(B, H, D, device=qkv.device, dtype=qkv.dtype)
@@ -806,6 +827,15 @@ def _mmha_hip(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0):
         mlen = mask.shape[1]
         if t_dev is None and mlen < t + 1:
             raise ValueError(f"mmha_decode: mask covers {mlen} positions, need {t + 1}")
+    if gqa:
+        R._STATS[('mmha_decode_gqa', 'hip')] += 1
+        _native.lib().mmha_gqa_decode(_ptr(qkv), _ptr(cache), _ptr(mask) if mask is not None else 0,
+                                      _ptr(ws), _ptr(out), B, H, KVH, L, D, int(t),
+                                      _ptr(t_dev) if t_dev is not None else 0, splits, mlen,
+                                      1.0 / math.sqrt(D), _dt(qkv), _stream(),
+                                      _ptr(seq_lens) if seq_lens is not None else 0,
+                                      _ptr(rotary) if rotary is not None else 0, int(rotary_dims))
+        return out
     _native.lib().mmha_decode(_ptr(qkv), _ptr(cache), _ptr(mask) if mask is not None else 0,
                               _ptr(ws), _ptr(out), B, H, L, D, int(t),
                               _ptr(t_dev) if t_dev is not None else 0, splits, mlen,
@@ -813,6 +843,9 @@ def _mmha_hip(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0):
                               _ptr(seq_lens) if seq_lens is not None else 0,
                               _ptr(rotary) if rotary is not None else 0, int(rotary_dims))
     return out
+
+
+GQA_RATIOS = (2, 4, 8)   # query heads per K/V head the HIP grouped-query kernel is built for
 
 
 def rotary_in_kernel(head_dim, rotary_dims):
@@ -833,9 +866,26 @@ def mmha_decode(qkv, cache, time_step, mask=None, seq_lens=None, rotary=None, ro
     ``time_step`` are validated here (0 <= t_b <= time_step < L); device values are not
     synced — a sequence whose position is out of range gets a zero output and no write.
     ``rotary`` ((cos, sin) or a stacked tensor, [2, B, D]) rotates q and the new k with the
-    half-split rule inside each of ``rotary_dims`` chunks of the head dim before attention."""
+    half-split rule inside each of ``rotary_dims`` chunks of the head dim before attention.
+
+    Grouped-query attention: a 3-D ``qkv`` [B, H + 2*KVH, D] (the H query heads, then the KVH
+    k heads, then the KVH v heads) with ``cache`` [2, B, KVH, L, D]; query head ``h`` reads
+    K/V head ``h // (H // KVH)``. ``KVH == H`` is the 4-D form; on the GPU the ratio H / KVH
+    must be one of ``GQA_RATIOS``."""
     if not isinstance(time_step, torch.Tensor):
         time_step = int(time_step)
+    if qkv.dim() == 3:
+        if cache.dim() != 5 or cache.shape[1] != qkv.shape[0] or cache.shape[4] != qkv.shape[2]:
+            raise ValueError(f"mmha_decode: cache {tuple(cache.shape)} does not fit qkv "
+                             f"{tuple(qkv.shape)}; need [2, B, KVH, L, D]")
+        KVH = cache.shape[2]
+        H = qkv.shape[1] - 2 * KVH
+        if H <= 0 or H % KVH != 0:
+            raise ValueError(f"mmha_decode: qkv has {qkv.shape[1]} head rows and the cache {KVH} "
+                             f"K/V heads; {qkv.shape[1]} - 2*{KVH} query heads must be a "
+                             f"positive multiple of {KVH}")
+        if H == KVH:
+            qkv = qkv.reshape(qkv.shape[0], 3, H, qkv.shape[2])
     if seq_lens is None and rotary is None:
         return R.dispatch('mmha_decode', qkv, qkv.contiguous(), cache, time_step, mask)
     B, D = qkv.shape[0], qkv.shape[-1]

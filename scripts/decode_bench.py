@@ -1,6 +1,6 @@
 """Decode-attention bandwidth: the HIP split-K kernel (K.mmha_decode) vs torch SDPA over
 the same KV cache, a ragged batch (per-sequence seq_lens) next to its padded-and-masked twin,
-and end-to-end FusedMultiTransformer decode steps/s.
+grouped-query attention next to the expanded multi-head cache and the byte floor, and end-to-end FusedMultiTransformer decode steps/s.
 
 usage: python scripts/decode_bench.py [--quick]"""
 import argparse
@@ -67,6 +67,28 @@ def main():
                           masked_us=round(masked * 1e6, 1), valid_GB=round(gb, 4),
                           ragged_TBps=round(gb / ragged / 1e3, 2),
                           masked_TBps=round(gb / masked / 1e3, 2))), flush=True)
+    # grouped-query attention (KVH K/V heads shared by H query heads): the GQA kernel on the
+    # KVH-head cache, next to the plain kernel on the cache expanded to H heads (the only way
+    # to run such a model without it) and the plain kernel at H = KVH (the same cache bytes with
+    # 1/R of the scoring work: the byte floor). TB/s counts the KVH-head cache bytes.
+    for H, KVH in ((32, 8), (64, 8)):
+        B, D, t, r = 8, 128, 4095, H // KVH
+        row = torch.randn(B, H + 2 * KVH, D, device='cuda', dtype=torch.bfloat16)
+        cache = torch.randn(2, B, KVH, t + 1, D, device='cuda', dtype=torch.bfloat16)
+        gqa = bench(lambda: K.mmha_decode(row, cache, t))
+        qkv_x = torch.stack([row[:, :H], row[:, H:H + KVH].repeat_interleave(r, 1),
+                             row[:, H + KVH:].repeat_interleave(r, 1)], 1).contiguous()
+        cache_x = cache.repeat_interleave(r, 2).contiguous()
+        expanded = bench(lambda: K.mmha_decode(qkv_x, cache_x, t))
+        del cache_x
+        qkv_s = torch.randn(B, 3, KVH, D, device='cuda', dtype=torch.bfloat16)
+        same = bench(lambda: K.mmha_decode(qkv_s, cache, t))
+        gb = 2 * B * KVH * (t + 1) * D * 2 / 1e9
+        print(json.dumps(dict(B=B, H=H, KVH=KVH, D=D, ctx=t + 1, gqa_us=round(gqa * 1e6, 1),
+                              expanded_us=round(expanded * 1e6, 1),
+                              same_bytes_us=round(same * 1e6, 1), kv_GB=round(gb, 4),
+                              gqa_TBps=round(gb / gqa / 1e3, 2),
+                              splits=K._native.lib().mmha_splits(B, KVH, t))), flush=True)
     # end-to-end decode: 24-layer 2048-wide model (GPT-3 1.3B shape), batch 8
     import paddle_ray_amd as paddle
     from paddle_ray_amd.incubate.nn import FusedMultiTransformer
