@@ -13,12 +13,12 @@ namespace py = pybind11;
 typedef uintptr_t P;
 
 extern "C" {
-void pra_layernorm_fwd(const void*, const void*, const void*, void*, float*, float*, int, int, float, int, int,
+int pra_layernorm_fwd(const void*, const void*, const void*, void*, float*, float*, int, int, float, int, int,
                        hipStream_t);
-void pra_layernorm_bwd(const void*, const void*, const void*, const float*, const float*, void*, float*, float*, int,
+int pra_layernorm_bwd(const void*, const void*, const void*, const float*, const float*, void*, float*, float*, int,
                        int, int, int, int, hipStream_t);
-void pra_rmsnorm_fwd(const void*, const void*, void*, float*, int, int, float, int, int, hipStream_t);
-void pra_rmsnorm_bwd(const void*, const void*, const void*, const float*, void*, float*, int, int, int, int, int,
+int pra_rmsnorm_fwd(const void*, const void*, void*, float*, int, int, float, int, int, hipStream_t);
+int pra_rmsnorm_bwd(const void*, const void*, const void*, const float*, void*, float*, int, int, int, int, int,
                      hipStream_t);
 void pra_colsum(const float*, void*, int, int, int, hipStream_t);
 void pra_softmax_fwd(const void*, void*, int, int, int, hipStream_t);
@@ -50,9 +50,9 @@ void pra_momentum_mt(const int64_t*, const float*, const int64_t*, int, float, f
 void pra_sumsq_accum(const void*, float*, int64_t, int, hipStream_t);
 void pra_flash_bwd_pre(const void*, const void*, float*, int, int, int, int, int, hipStream_t);
 int pra_adl_supported(int);
-void pra_adl_fwd(const void*, const void*, const void*, const void*, const void*, void*, void*, float*, float*, int,
+int pra_adl_fwd(const void*, const void*, const void*, const void*, const void*, void*, void*, float*, float*, int,
                  int, float, float, uint64_t, uint64_t, const uint64_t*, int, int, hipStream_t);
-void pra_adl_bwd(const void*, const void*, const void*, const void*, const float*, const float*, void*, void*, float*,
+int pra_adl_bwd(const void*, const void*, const void*, const void*, const float*, const float*, void*, void*, float*,
                  float*, float*, int, int, int, float, uint64_t, uint64_t, const uint64_t*, int, int, hipStream_t);
 void pra_colsum16(const float*, void*, int, int, int, int, hipStream_t);
 int pra_flash_fwd(const void*, const void*, const void*, void*, float*, int, int, int, int, int, const int64_t*, float,
@@ -203,20 +203,25 @@ PYBIND11_MODULE(_pra_hip, m) {
     check_launch("colsum_partials");
   });
   m.def("layernorm_fwd", [](P x, P w, P b, P y, P mean, P rstd, int rows, int cols, float eps, int dtx, int dtw, P s) {
-    pra_layernorm_fwd(CV(x), CV(w), CV(b), V(y), F(mean), F(rstd), rows, cols, eps, dtx, dtw, S(s));
+    if (pra_layernorm_fwd(CV(x), CV(w), CV(b), V(y), F(mean), F(rstd), rows, cols, eps, dtx, dtw, S(s)) != 0)
+      throw std::invalid_argument("layernorm_fwd: unsupported dtype pair");
     check_launch("layernorm_fwd");
   });
   m.def("layernorm_bwd", [](P dy, P x, P w, P mean, P rstd, P dx, P pw, P pb, int rows, int cols, int nblk, int dtx,
                             int dtw, P s) {
-    pra_layernorm_bwd(CV(dy), CV(x), CV(w), CF(mean), CF(rstd), V(dx), F(pw), F(pb), rows, cols, nblk, dtx, dtw, S(s));
+    if (pra_layernorm_bwd(CV(dy), CV(x), CV(w), CF(mean), CF(rstd), V(dx), F(pw), F(pb), rows, cols, nblk, dtx, dtw,
+                          S(s)) != 0)
+      throw std::invalid_argument("layernorm_bwd: unsupported dtype pair");
     check_launch("layernorm_bwd");
   });
   m.def("rmsnorm_fwd", [](P x, P w, P y, P rstd, int rows, int cols, float eps, int dtx, int dtw, P s) {
-    pra_rmsnorm_fwd(CV(x), CV(w), V(y), F(rstd), rows, cols, eps, dtx, dtw, S(s));
+    if (pra_rmsnorm_fwd(CV(x), CV(w), V(y), F(rstd), rows, cols, eps, dtx, dtw, S(s)) != 0)
+      throw std::invalid_argument("rmsnorm_fwd: unsupported dtype pair");
     check_launch("rmsnorm_fwd");
   });
   m.def("rmsnorm_bwd", [](P dy, P x, P w, P rstd, P dx, P pw, int rows, int cols, int nblk, int dtx, int dtw, P s) {
-    pra_rmsnorm_bwd(CV(dy), CV(x), CV(w), CF(rstd), V(dx), F(pw), rows, cols, nblk, dtx, dtw, S(s));
+    if (pra_rmsnorm_bwd(CV(dy), CV(x), CV(w), CF(rstd), V(dx), F(pw), rows, cols, nblk, dtx, dtw, S(s)) != 0)
+      throw std::invalid_argument("rmsnorm_bwd: unsupported dtype pair");
     check_launch("rmsnorm_bwd");
   });
   m.def("colsum", [](P part, P out, int nblk, int cols, int dt, P s) {
@@ -321,14 +326,16 @@ PYBIND11_MODULE(_pra_hip, m) {
   m.def("adl_supported", [](int cols) { return pra_adl_supported(cols); });
   m.def("adl_fwd", [](P x, P h, P hb, P w, P b, P r, P y, P mean, P rstd, int rows, int cols, float eps, float p,
                       uint64_t seed, uint64_t off, P dseq, int dt, int dtw, P s) {
-    pra_adl_fwd(CV(x), CV(h), CV(hb), CV(w), CV(b), V(r), V(y), F(mean), F(rstd), rows, cols, eps, p, seed, off,
-                reinterpret_cast<const uint64_t*>(dseq), dt, dtw, S(s));
+    if (pra_adl_fwd(CV(x), CV(h), CV(hb), CV(w), CV(b), V(r), V(y), F(mean), F(rstd), rows, cols, eps, p, seed, off,
+                    reinterpret_cast<const uint64_t*>(dseq), dt, dtw, S(s)) != 0)
+      throw std::invalid_argument("adl_fwd: unsupported dtype pair");
     check_launch("adl_fwd");
   });
   m.def("adl_bwd", [](P dy, P dro, P r, P w, P mean, P rstd, P dri, P dh, P pw, P pb, P pbias, int rows, int cols,
                       int nblk, float p, uint64_t seed, uint64_t off, P dseq, int dt, int dtw, P s) {
-    pra_adl_bwd(CV(dy), CV(dro), CV(r), CV(w), CF(mean), CF(rstd), V(dri), V(dh), F(pw), F(pb), F(pbias), rows, cols,
-                nblk, p, seed, off, reinterpret_cast<const uint64_t*>(dseq), dt, dtw, S(s));
+    if (pra_adl_bwd(CV(dy), CV(dro), CV(r), CV(w), CF(mean), CF(rstd), V(dri), V(dh), F(pw), F(pb), F(pbias), rows,
+                    cols, nblk, p, seed, off, reinterpret_cast<const uint64_t*>(dseq), dt, dtw, S(s)) != 0)
+      throw std::invalid_argument("adl_bwd: unsupported dtype pair");
     check_launch("adl_bwd");
   });
   m.def("colsum16", [](P part, P out, int nblk, int cols, int dt, P s) {

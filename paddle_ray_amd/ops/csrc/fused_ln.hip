@@ -359,10 +359,12 @@ using namespace pra;
 extern "C" {
 int pra_adl_supported(int cols) { return (cols % 8 == 0 && cols <= 4096) ? 1 : 0; }
 
-void pra_adl_fwd(const void* x, const void* h, const void* hbias, const void* w, const void* b, void* r_out,
-                 void* y, float* mean, float* rstd, int rows, int cols, float eps, float p, uint64_t seed,
-                 uint64_t offset, const uint64_t* dseq, int dt, int dtw, hipStream_t s) {
-  if (!rows) return;
+int pra_adl_fwd(const void* x, const void* h, const void* hbias, const void* w, const void* b, void* r_out,
+                void* y, float* mean, float* rstd, int rows, int cols, float eps, float p, uint64_t seed,
+                uint64_t offset, const uint64_t* dseq, int dt, int dtw, hipStream_t s) {
+  // the weight is read as dt or as fp32; any other pair would misread it: launch nothing
+  if ((dt != kF32 && dt != kF16 && dt != kBF16) || (dtw != dt && dtw != kF32)) return -1;
+  if (!rows) return 0;
   uint32_t thr = (h && p > 0.f) ? (uint32_t)(p * 65536.f + 0.5f) : 0u;
   float scale = thr ? 1.f / (1.f - p) : 1.f;
   dim3 grid((rows + 3) / 4);
@@ -375,13 +377,15 @@ void pra_adl_fwd(const void* x, const void* h, const void* hbias, const void* w,
     else { ADL_DISPATCH_C(cols, K_FWD, TX, float); }
   });
 #undef K_FWD
+  return 0;
 }
 
-void pra_adl_bwd(const void* dy, const void* dr_out, const void* r, const void* w, const float* mean,
-                 const float* rstd, void* dr_in, void* dh, float* pw, float* pb, float* pbias, int rows, int cols,
-                 int nblk, float p, uint64_t seed, uint64_t offset, const uint64_t* dseq, int dt, int dtw,
-                 hipStream_t s) {
-  if (!rows) return;
+int pra_adl_bwd(const void* dy, const void* dr_out, const void* r, const void* w, const float* mean,
+                const float* rstd, void* dr_in, void* dh, float* pw, float* pb, float* pbias, int rows, int cols,
+                int nblk, float p, uint64_t seed, uint64_t offset, const uint64_t* dseq, int dt, int dtw,
+                hipStream_t s) {
+  if ((dt != kF32 && dt != kF16 && dt != kBF16) || (dtw != dt && dtw != kF32)) return -1;
+  if (!rows) return 0;
   uint32_t thr = (dh && p > 0.f) ? (uint32_t)(p * 65536.f + 0.5f) : 0u;
   float scale = thr ? 1.f / (1.f - p) : 1.f;
   size_t lds = (size_t)4 * cols * sizeof(float);
@@ -400,6 +404,7 @@ void pra_adl_bwd(const void* dy, const void* dr_out, const void* r, const void* 
     else { ADL_DISPATCH_C(cols, K_BWD, TX, float); }
   });
 #undef K_BWD
+  return 0;
 }
 
 // njobs <= 3 reductions part[j] [nblk][cols] -> out[j] (+= when acc[j]), one dtype; cols % 4 == 0

@@ -253,29 +253,36 @@ scalar:
 
 using namespace pra;
 
+// Runs the statement for (TX, TW) with TW = TX or float and returns 0 from the enclosing function;
+// any other pair (unknown dtx, or a dtw that is neither dtx nor fp32) falls through to the
+// caller's `return -1`: nothing is launched and the binding raises.
 #define PRA_DISPATCH_TW(dtx, dtw, ...)                                                     \
   PRA_DISPATCH_FLOAT(dtx, TX, {                                                            \
-    if (dtw == dtx) { using TW = TX; __VA_ARGS__; }                                        \
-    else if (dtw == kF32) { using TW = float; __VA_ARGS__; }                               \
+    if (dtw == dtx) { using TW = TX; __VA_ARGS__; return 0; }                              \
+    else if (dtw == kF32) { using TW = float; __VA_ARGS__; return 0; }                     \
   })
 
 extern "C" {
-void pra_layernorm_fwd(const void* x, const void* w, const void* b, void* y, float* mean, float* rstd,
-                       int rows, int cols, float eps, int dtx, int dtw, hipStream_t s) {
+int pra_layernorm_fwd(const void* x, const void* w, const void* b, void* y, float* mean, float* rstd,
+                      int rows, int cols, float eps, int dtx, int dtw, hipStream_t s) {
   PRA_DISPATCH_TW(dtx, dtw, (launch_fwd<TX, TW, true>(x, w, b, y, mean, rstd, rows, cols, eps, s)));
+  return -1;
 }
-void pra_layernorm_bwd(const void* dy, const void* x, const void* w, const float* mean, const float* rstd,
-                       void* dx, float* pw, float* pb, int rows, int cols, int nblk, int dtx, int dtw,
-                       hipStream_t s) {
+int pra_layernorm_bwd(const void* dy, const void* x, const void* w, const float* mean, const float* rstd,
+                      void* dx, float* pw, float* pb, int rows, int cols, int nblk, int dtx, int dtw,
+                      hipStream_t s) {
   PRA_DISPATCH_TW(dtx, dtw, (launch_bwd<TX, TW, true>(dy, x, w, mean, rstd, dx, pw, pb, rows, cols, nblk, s)));
+  return -1;
 }
-void pra_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int rows, int cols, float eps,
-                     int dtx, int dtw, hipStream_t s) {
+int pra_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int rows, int cols, float eps,
+                    int dtx, int dtw, hipStream_t s) {
   PRA_DISPATCH_TW(dtx, dtw, (launch_fwd<TX, TW, false>(x, w, nullptr, y, nullptr, rstd, rows, cols, eps, s)));
+  return -1;
 }
-void pra_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rstd, void* dx, float* pw,
-                     int rows, int cols, int nblk, int dtx, int dtw, hipStream_t s) {
+int pra_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rstd, void* dx, float* pw,
+                    int rows, int cols, int nblk, int dtx, int dtw, hipStream_t s) {
   PRA_DISPATCH_TW(dtx, dtw, (launch_bwd<TX, TW, false>(dy, x, w, nullptr, rstd, dx, pw, nullptr, rows, cols, nblk, s)));
+  return -1;
 }
 void pra_colsum(const float* part, void* out, int nblk, int cols, int dto, hipStream_t s) {
   PRA_DISPATCH_FLOAT(dto, TO, hipLaunchKernelGGL((colsum_kernel<TO>), dim3((cols + 255) / 256), dim3(256), 0, s,

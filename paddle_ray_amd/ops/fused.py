@@ -55,6 +55,35 @@ def _check_dtypes(op, *pairs):
             raise TypeError(f"{op}: operand dtypes differ ({a.dtype} vs {b.dtype})")
 
 
+def _norm_params(x, w, b=None):
+    """Norm weight / bias in a dtype the kernels are compiled for.
+
+    The LayerNorm, RMSNorm and add+dropout+LayerNorm kernels read ``w`` / ``b`` either in the
+    activation dtype or in fp32 (the AMP layout) and in nothing else. Policy, the same on the
+    ``ref`` and ``hip`` backends: ``w`` decides (``b`` when there is no ``w``); if its dtype is
+    neither ``x.dtype`` nor fp32 both parameters are CAST TO FP32 -- exactly what the ``ref``
+    kernels compute (``w.float()``) -- and ``b`` always follows ``w``. Nothing raises. Autograd
+    casts the returned dw / db back to the dtype of the tensors the caller passed."""
+    lead = w if w is not None else b
+    if lead is None:
+        return w, b
+    dt = lead.dtype if lead.dtype in (x.dtype, torch.float32) else torch.float32
+    return _like(w, dt), _like(b, dt)
+
+
+def _wdt(op, x2, w, b=None):
+    """dtype code the kernel reads ``w`` / ``b`` with; the last host-side guard in front of a
+    launch (the autograd Functions never get here with another pair, see ``_norm_params``)."""
+    _check_dtypes(op, (w, b))
+    lead = w if w is not None else b
+    if lead is None:
+        return _dt(x2)
+    if lead.dtype != x2.dtype and lead.dtype != torch.float32:
+        raise TypeError(f"{op}: weight dtype {lead.dtype} with activations in {x2.dtype} "
+                        f"(kernels take {x2.dtype} or float32)")
+    return _dt(lead)
+
+
 # =============================================================================
 # LayerNorm (last-dim normalisation over `cols`)
 # kernel keys: the dtypes each HIP kernel is compiled for (registry dispatch falls back to the
@@ -78,7 +107,8 @@ def _ln_fwd_ref(x2, w, b, eps):
 
 
 @R.register_kernel('layer_norm_bwd', 'ref')
-def _ln_bwd_ref(dy, x2, w, mean, rstd, need_dw, need_db):
+def _ln_bwd_ref(dy, x2, w, mean, rstd, need_dw, need_db, pdt=None):
+    """pdt: dtype of db when there is no w (the bias's own dtype; default x2's)."""
     xf, dyf = x2.float(), dy.float()
     xhat = (xf - mean[:, None]) * rstd[:, None]
     g = dyf * w.float() if w is not None else dyf
@@ -86,7 +116,7 @@ def _ln_bwd_ref(dy, x2, w, mean, rstd, need_dw, need_db):
     c2 = g.mean(-1, keepdim=True)
     dx = (g - c2 - xhat * c1) * rstd[:, None]
     dw = (dyf * xhat).sum(0).to(w.dtype) if (w is not None and need_dw) else None
-    db = dyf.sum(0).to(w.dtype if w is not None else dy.dtype) if need_db else None
+    db = dyf.sum(0).to(w.dtype if w is not None else (pdt or dy.dtype)) if need_db else None
     return dx.to(x2.dtype), dw, db
 
 
@@ -108,13 +138,12 @@ def _adl_nblk(rows):
 
 @R.register_kernel('layer_norm_fwd', 'hip', dtypes=_FLOATS)
 def _ln_fwd_hip(x2, w, b, eps):
-    _check_dtypes('layer_norm', (w, b))
+    dtw = _wdt('layer_norm', x2, w, b)
     L = _native.lib()
     rows, cols = x2.shape
     y = torch.empty_like(x2)
     mean = torch.empty(rows, device=x2.device, dtype=torch.float32)
     rstd = torch.empty(rows, device=x2.device, dtype=torch.float32)
-    dtw = _dt(w) if w is not None else _dt(x2)
     if _adl_ok(cols):
         L.adl_fwd(_ptr(x2), 0, 0, _ptr(w), _ptr(b), 0, _ptr(y), _ptr(mean), _ptr(rstd), rows, cols,
                   float(eps), 0.0, 0, 0, 0, _dt(x2), dtw, _stream())
@@ -125,12 +154,12 @@ def _ln_fwd_hip(x2, w, b, eps):
 
 
 @R.register_kernel('layer_norm_bwd', 'hip', dtypes=_FLOATS)
-def _ln_bwd_hip(dy, x2, w, mean, rstd, need_dw, need_db):
+def _ln_bwd_hip(dy, x2, w, mean, rstd, need_dw, need_db, pdt=None):
     L = _native.lib()
     rows, cols = x2.shape
     dx = torch.empty_like(x2)
-    pdt = w.dtype if w is not None else x2.dtype
-    dtw = _dt(w) if w is not None else _dt(x2)
+    pdt = w.dtype if w is not None else (pdt or x2.dtype)
+    dtw = _wdt('layer_norm_grad', x2, w)
     dy = dy.contiguous()
     if _adl_ok(cols):
         nblk = _adl_nblk(rows)
@@ -162,11 +191,11 @@ class LayerNormFn(torch.autograd.Function):
         shp = x.shape
         cols = w.numel() if w is not None else shp[-1]
         x2 = x.contiguous().view(-1, cols)
-        if w is not None:
-            b = _like(b, w.dtype)
+        w, b = _norm_params(x2, w, b)
         y, mean, rstd = R.dispatch('layer_norm_fwd', x2, x2, w, b, eps)
         ctx.save_for_backward(x2, w, mean, rstd)
         ctx.has_b = b is not None
+        ctx.pdt = b.dtype if b is not None else None   # a bias without a weight: db in ITS dtype
         ctx.shp = shp
         return y.view(shp)
 
@@ -175,11 +204,13 @@ class LayerNormFn(torch.autograd.Function):
         x2, w, mean, rstd = ctx.saved_tensors
         dy2 = _like(dy, x2.dtype).contiguous().view(x2.shape)
         dx, dw, db = R.dispatch('layer_norm_bwd', x2, dy2, x2, w, mean, rstd,
-                                ctx.needs_input_grad[1], ctx.has_b and ctx.needs_input_grad[2])
+                                ctx.needs_input_grad[1], ctx.has_b and ctx.needs_input_grad[2], ctx.pdt)
         return dx.view(ctx.shp), dw, db, None
 
 
 def layer_norm(x, w, b, eps=1e-5):
+    """LayerNorm over the last dim. ``w`` / ``b`` in x's dtype or fp32 are used as they are; any
+    other dtype is cast to fp32 on both backends, never refused (``_norm_params``)."""
     return LayerNormFn.apply(x, w, b, eps)
 
 
@@ -279,8 +310,8 @@ def _adl_fwd_ref(x2, h2, hb, w, b, p, eps, seed):
 
 
 @R.register_kernel('add_dropout_ln_bwd', 'ref')
-def _adl_bwd_ref(dy, dr_out, r, w, mean, rstd, p, seed, need_dw, need_db, need_dhb):
-    dx, dw, db = _ln_bwd_ref(dy, r, w, mean, rstd, need_dw, need_db)
+def _adl_bwd_ref(dy, dr_out, r, w, mean, rstd, p, seed, need_dw, need_db, need_dhb, pdt=None):
+    dx, dw, db = _ln_bwd_ref(dy, r, w, mean, rstd, need_dw, need_db, pdt)
     dri = dx.float() + (dr_out.float() if dr_out is not None else 0)
     dh = dri
     if p > 0:
@@ -292,9 +323,11 @@ def _adl_bwd_ref(dy, dr_out, r, w, mean, rstd, p, seed, need_dw, need_db, need_d
 
 @R.register_kernel('add_dropout_ln_fwd', 'hip', dtypes=_FLOATS)
 def _adl_fwd_hip(x2, h2, hb, w, b, p, eps, seed, dseq=0):
-    _check_dtypes('add_dropout_layer_norm', (x2, h2), (x2, hb), (w, b))
+    _check_dtypes('add_dropout_layer_norm', (x2, h2), (x2, hb))
+    dtw = _wdt('add_dropout_layer_norm', x2, w, b)
     rows, cols = x2.shape
     if not _adl_ok(cols):
+        R._STATS[('add_dropout_ln_fwd', 'ref')] += 1  # a width the kernel does not take: visible in stats()
         return _adl_fwd_ref(x2, h2, hb, w, b, p, eps, seed)
     r = torch.empty_like(x2)
     y = torch.empty_like(x2)
@@ -302,29 +335,32 @@ def _adl_fwd_hip(x2, h2, hb, w, b, p, eps, seed, dseq=0):
     rstd = torch.empty(rows, device=x2.device, dtype=torch.float32)
     _native.lib().adl_fwd(_ptr(x2), _ptr(h2), _ptr(hb), _ptr(w), _ptr(b), _ptr(r), _ptr(y),
                           _ptr(mean), _ptr(rstd), rows, cols, float(eps), float(p), seed, 0, dseq,
-                          _dt(x2), _dt(w) if w is not None else _dt(x2), _stream())
+                          _dt(x2), dtw, _stream())
     return r, y, mean, rstd
 
 
 @R.register_kernel('add_dropout_ln_bwd', 'hip', dtypes=_FLOATS)
-def _adl_bwd_hip(dy, dr_out, r, w, mean, rstd, p, seed, need_dw, need_db, need_dhb, into=None, dseq=0):
+def _adl_bwd_hip(dy, dr_out, r, w, mean, rstd, p, seed, need_dw, need_db, need_dhb, into=None, dseq=0,
+                 pdt=None):
     """into: (w.grad, b.grad, hb.grad) or None per slot — those column sums are ADDED into the
     existing gradient by the reduction kernel and None is returned in their place (no
     AccumulateGrad add kernels for the LayerNorm / bias parameters)."""
     _check_dtypes('add_dropout_layer_norm_grad', (r, dy), (r, dr_out))
+    dtw = _wdt('add_dropout_layer_norm_grad', r, w)
     rows, cols = r.shape
     if not _adl_ok(cols):
-        return _adl_bwd_ref(dy, dr_out, r, w, mean, rstd, p, seed, need_dw, need_db, need_dhb)
+        R._STATS[('add_dropout_ln_bwd', 'ref')] += 1
+        return _adl_bwd_ref(dy, dr_out, r, w, mean, rstd, p, seed, need_dw, need_db, need_dhb, pdt)
     L = _native.lib()
     dri = torch.empty_like(r)
     dh = torch.empty_like(r)
     nblk = _adl_nblk(rows)
     part = torch.empty((3, nblk, cols), device=r.device, dtype=torch.float32)
-    pdt = w.dtype if w is not None else r.dtype
+    pdt = w.dtype if w is not None else (pdt or r.dtype)
     L.adl_bwd(_ptr(dy), _ptr(dr_out), _ptr(r), _ptr(w), _ptr(mean), _ptr(rstd), _ptr(dri),
               _ptr(dh), _ptr(part[0]) if need_dw else 0, _ptr(part[1]) if need_db else 0,
               _ptr(part[2]) if need_dhb else 0, rows, cols, nblk, float(p), seed, 0, dseq, _dt(r),
-              _dt(w) if w is not None else _dt(r), _stream())
+              dtw, _stream())
     outs, jobs = [], []
     into = into or (None, None, None)
     for need, i, dt in ((need_dw, 0, pdt), (need_db, 1, pdt), (need_dhb, 2, r.dtype)):
@@ -364,8 +400,7 @@ class AddDropoutLNFn(torch.autograd.Function):
         x2 = x.contiguous().view(-1, cols)
         h2 = _like(h, x.dtype).contiguous().view(-1, cols)
         hb = _like(hb, x.dtype)
-        if w is not None:
-            b = _like(b, w.dtype)
+        w, b = _norm_params(x2, w, b)
         seed = _dropout_seed() if p > 0 else 0
         dseq, ctx.gseq = _graph_seq(x.device) if p > 0 else (0, None)
         if dseq and R.select_backend(x2, 'add_dropout_ln_fwd') == 'hip':
@@ -376,6 +411,7 @@ class AddDropoutLNFn(torch.autograd.Function):
         ctx.params = (w, b, hb)
         ctx.p, ctx.seed, ctx.shp, ctx.dseq = p, seed, shp, dseq
         ctx.has_b, ctx.has_hb = b is not None, hb is not None
+        ctx.pdt = b.dtype if b is not None else None
         return r.view(shp), y.view(shp)
 
     @staticmethod
@@ -391,14 +427,15 @@ class AddDropoutLNFn(torch.autograd.Function):
         if r.is_cuda and R.select_backend(r, 'add_dropout_ln_bwd') == 'hip':
             pw, pb, phb = ctx.params
             into = (_acc_target(pw), _acc_target(pb), _acc_target(phb))
-            dri, dh, dw, db, dhb = _adl_bwd_hip(*args[1:], into=into, dseq=ctx.dseq)
+            dri, dh, dw, db, dhb = _adl_bwd_hip(*args[1:], into=into, dseq=ctx.dseq, pdt=ctx.pdt)
         else:
-            dri, dh, dw, db, dhb = R.dispatch('add_dropout_ln_bwd', *args)
+            dri, dh, dw, db, dhb = R.dispatch('add_dropout_ln_bwd', *args, pdt=ctx.pdt)
         return dri.view(ctx.shp), dh.view(ctx.shp), dhb, dw, db, None, None
 
 
 def add_dropout_layer_norm(x, h, hbias, w, b, p=0.0, eps=1e-5, training=True):
-    """(r, y) with r = x + dropout(h + hbias), y = LayerNorm(r)·w + b."""
+    """(r, y) with r = x + dropout(h + hbias), y = LayerNorm(r)·w + b. ``w`` / ``b`` dtype policy
+    as for ``layer_norm`` (``_norm_params``); ``h`` / ``hbias`` are brought to x's dtype."""
     p = p if training else 0.0
     if p > 0 and x.is_cuda and torch.cuda.is_current_stream_capturing() and not _adl_ok(x.shape[-1]):
         # a width the kernel does not take: torch's graph-aware dropout RNG under capture
@@ -439,7 +476,7 @@ def _rms_fwd_hip(x2, w, eps):
     y = torch.empty_like(x2)
     rstd = torch.empty(rows, device=x2.device, dtype=torch.float32)
     L.rmsnorm_fwd(_ptr(x2), _ptr(w), _ptr(y), _ptr(rstd), rows, cols, float(eps), _dt(x2),
-                  _dt(w) if w is not None else _dt(x2), _stream())
+                  _wdt('rms_norm', x2, w), _stream())
     return y, rstd
 
 
@@ -451,7 +488,7 @@ def _rms_bwd_hip(dy, x2, w, rstd, need_dw):
     nblk = _colsum_nblk(rows)
     part = torch.empty((nblk, cols), device=x2.device, dtype=torch.float32)
     L.rmsnorm_bwd(_ptr(dy.contiguous()), _ptr(x2), _ptr(w), _ptr(rstd), _ptr(dx), _ptr(part),
-                  rows, cols, nblk, _dt(x2), _dt(w) if w is not None else _dt(x2), _stream())
+                  rows, cols, nblk, _dt(x2), _wdt('rms_norm_grad', x2, w), _stream())
     dw = None
     if need_dw and w is not None:
         dw = torch.empty(cols, device=x2.device, dtype=w.dtype)
@@ -464,6 +501,7 @@ class RMSNormFn(torch.autograd.Function):
     def forward(ctx, x, w, eps):
         shp = x.shape
         x2 = x.contiguous().view(-1, shp[-1])
+        w, _ = _norm_params(x2, w)
         y, rstd = R.dispatch('rms_norm_fwd', x2, x2, w, eps)
         ctx.save_for_backward(x2, w, rstd)
         ctx.shp = shp
@@ -478,6 +516,7 @@ class RMSNormFn(torch.autograd.Function):
 
 
 def rms_norm(x, w, eps=1e-6):
+    """RMSNorm over the last dim; ``w`` dtype policy as for ``layer_norm`` (``_norm_params``)."""
     return RMSNormFn.apply(x, w, eps)
 
 
@@ -534,11 +573,18 @@ def softmax_lastdim(x):
 # =============================================================================
 # Fused softmax + cross-entropy (hard labels, ignore_index)
 # =============================================================================
+def _ce_valid(labels, ignore_index, V):
+    """Rows that contribute: a label equal to ``ignore_index`` OR outside ``[0, V)`` gives loss 0
+    and a zero gradient row -- the policy of ``ce_fwd_k`` / ``ce_bwd_k`` and of the ``vp_ce_*``
+    kernels, the same on both backends."""
+    return (labels != ignore_index) & (labels >= 0) & (labels < V)
+
+
 @R.register_kernel('softmax_ce_fwd', 'ref')
 def _ce_fwd_ref(logits, labels, ignore_index):
     lf = logits.float()
     lse = torch.logsumexp(lf, -1)
-    valid = labels != ignore_index
+    valid = _ce_valid(labels, ignore_index, lf.shape[1])
     safe = torch.where(valid, labels, torch.zeros_like(labels))
     picked = lf.gather(-1, safe[:, None]).squeeze(-1)
     loss = torch.where(valid, lse - picked, torch.zeros_like(lse))
@@ -548,7 +594,7 @@ def _ce_fwd_ref(logits, labels, ignore_index):
 @R.register_kernel('softmax_ce_bwd', 'ref')
 def _ce_bwd_ref(logits, labels, lse, dloss, ignore_index):
     p = torch.exp(logits.float() - lse[:, None])
-    valid = labels != ignore_index
+    valid = _ce_valid(labels, ignore_index, logits.shape[1])
     safe = torch.where(valid, labels, torch.zeros_like(labels))
     p.scatter_add_(-1, safe[:, None], -torch.ones_like(p[:, :1]))
     g = p * (dloss * valid.float())[:, None]
