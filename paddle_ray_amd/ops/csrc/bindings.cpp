@@ -32,10 +32,8 @@ void pra_vp_ce_bwd(const void*, const int64_t*, const float*, const float*, void
                    int, hipStream_t);
 const char* pra_build_info();
 int pra_mmha_splits(int, int, int);
-int pra_mmha_decode(const void*, void*, const float*, float*, void*, int, int, int, int, int, const int*, int, int,
-                    float, int, const int*, const float*, int, hipStream_t);
-int pra_mmha_gqa_decode(const void*, void*, const float*, float*, void*, int, int, int, int, int, int, const int*, int,
-                        int, float, int, const int*, const float*, int, hipStream_t);
+int pra_mmha_decode(const void*, void*, const float*, float*, void*, int, int, int, int, int, int, const int*, int,
+                    int, float, int, const int*, const float*, int, hipStream_t);
 void pra_bias_gelu_fwd(const void*, const void*, void*, int64_t, int, int, int, hipStream_t);
 void pra_bias_gelu_bwd(const void*, const void*, const void*, void*, int64_t, int, int, int, hipStream_t);
 void pra_adamw_mt(const int64_t*, const float*, const int64_t*, int, float, float, float, float, float, float, float,
@@ -267,24 +265,14 @@ PYBIND11_MODULE(_pra_hip, m) {
     return id;
   });
   m.def("mmha_splits", [](int B, int H, int t) { return pra_mmha_splits(B, H, t); });
-  m.def("mmha_decode", [](P qkv, P cache, P mask, P ws, P out, int B, int H, int L, int D, int t, P t_dev,
+  m.def("mmha_decode", [](P qkv, P cache, P mask, P ws, P out, int B, int H, int KVH, int L, int D, int t, P t_dev,
                           int splits, int mask_len, float scale, int dt, P s, P seq_lens, P rot, int rot_dims) {
-    if (pra_mmha_decode(CV(qkv), V(cache), CF(mask), F(ws), V(out), B, H, L, D, t,
+    if (pra_mmha_decode(CV(qkv), V(cache), CF(mask), F(ws), V(out), B, H, KVH, L, D, t,
                         reinterpret_cast<const int*>(t_dev), splits, mask_len, scale, dt,
                         reinterpret_cast<const int*>(seq_lens), CF(rot), rot_dims, S(s)) != 0)
       throw std::invalid_argument(
-          "mmha_decode: unsupported head_dim/dtype/rotary_dims or time_step out of range");
+          "mmha_decode: unsupported head_dim/group ratio/dtype/rotary_dims or time_step out of range");
     check_launch("mmha_decode");
-  });
-  m.def("mmha_gqa_decode", [](P qkv, P cache, P mask, P ws, P out, int B, int H, int KVH, int L, int D, int t,
-                              P t_dev, int splits, int mask_len, float scale, int dt, P s, P seq_lens, P rot,
-                              int rot_dims) {
-    if (pra_mmha_gqa_decode(CV(qkv), V(cache), CF(mask), F(ws), V(out), B, H, KVH, L, D, t,
-                            reinterpret_cast<const int*>(t_dev), splits, mask_len, scale, dt,
-                            reinterpret_cast<const int*>(seq_lens), CF(rot), rot_dims, S(s)) != 0)
-      throw std::invalid_argument(
-          "mmha_gqa_decode: unsupported head_dim/group ratio/dtype/rotary_dims or time_step out of range");
-    check_launch("mmha_gqa_decode");
   });
   m.def("bias_gelu_fwd", [](P x, P b, P y, int64_t rows, int cols, int dt, int approx, P s) {
     pra_bias_gelu_fwd(CV(x), CV(b), V(y), rows, cols, dt, approx, S(s));

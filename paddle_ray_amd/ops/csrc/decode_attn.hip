@@ -1,31 +1,45 @@
-// Single-token (decode-phase) multi-head attention over a KV cache, for gfx950.
+// Single-token (decode-phase) attention over a KV cache, for gfx950: plain multi-head, ragged
+// batches with in-kernel rotary, and grouped-query (KVH < H K/V heads, each shared by
+// R = H / KVH consecutive query heads; query head h reads K/V head h / R), all from one kernel
+// template.
 //
 // Parity: the reference's masked multihead attention decoder kernel behind
 // fused_multi_transformer (paddle/fluid/operators/fused/fused_multi_transformer_op.cu.h,
-// mmha_launch_kernel): q·K over the cache positions [0, t], additive mask, softmax, ·V, and the
-// new token's K/V written into the cache at position t.
+// mmha_launch_kernel), with gqa_group_size = KVH: q·K over the cache positions [0, t], additive
+// mask, softmax, ·V, and the new token's K/V written into the cache at position t. The qkv row is
+// [H + 2*KVH, D] (the query heads, then KVH k heads, then KVH v heads), which for KVH = H is the
+// memory layout of [3, H, D]; the cache is [2, B, KVH, L, D].
 //
 // MI355X design (memory bound: every step streams the whole K/V cache once):
-//  * split-K "flash decoding": grid (splits, heads, batch); each workgroup owns a contiguous
-//    key range and keeps an online-softmax (max, sum, acc[D]) in registers; a second tiny
-//    kernel merges the splits. Splits are sized so a decode step launches >= ~1024
-//    workgroups (4 per CU) even at batch 1.
+//  * split-K "flash decoding": grid (splits, KVH, batch); each workgroup owns a contiguous
+//    key range of one K/V head and a second tiny kernel merges the splits. Splits are sized so
+//    a decode step launches >= ~1024 workgroups (4 per CU) even at batch 1.
 //  * G = D/8 lanes per key: each lane holds 8 of the D dims, so one key row (D*2 bytes) is
 //    read by G consecutive lanes as 16-byte vectors — fully coalesced — and a 64-wide wave
-//    works on 64/G keys at once. q·k is reduced over the G lanes with xor-shuffles that
-//    never leave the group.
-//  * two keys per lane-group per iteration are loaded before any math so >= 4 16-byte loads
-//    per lane are in flight.
+//    works on 64/G keys at once.
+//  * every K and V row is loaded ONCE and scored against all R query rows of its K/V head,
+//    which is the point of GQA on a memory-bound step. Each lane group keeps R scaled q rows
+//    and R online-softmax states (m, l, acc[8]) in registers.
+//  * two keys per lane group per iteration are loaded before any math so >= 4 16-byte loads
+//    per lane are in flight; the two keys share one rescale of each state. q·k is written on
+//    two-wide vectors (v_pk_fma_f32) and reduced over the G lanes with DPP operands on the
+//    adds, so the R reductions per key cost no LDS-pipe round trips.
+//  * key groups merge by xor-shuffle, waves through LDS, and lane group r of the workgroup
+//    finishes query head r. The partials are indexed by query head
+//    ((b*H + h)*splits + split), so mmha_combine_k merges them on grid (H, B) whatever R is.
 //  * the new token's K/V never round-trips through the cache: the workgroup that owns
-//    position t uses them from the qkv buffer and writes them into the cache (vector stores).
-//  * ragged batches (EXT instantiation; the plain one is compiled without any of it):
-//    seq_lens[b] replaces t for sequence b, so a short sequence streams only its own
+//    position t uses them from the qkv buffer and appends the K/V row of its K/V head (vector
+//    stores).
+//  * ragged batches and rotary (EXT instantiations; a non-EXT one is compiled without any of
+//    it): seq_lens[b] replaces t for sequence b, so a short sequence streams only its own
 //    [0, t_b) and workgroups whose key range lies past t_b leave at once with the empty
-//    partial (m = -inf, l = 0). rot [2, B, D] (cos, sin) rotates q and the new k in registers
-//    (half-split rule inside each of rot_dims chunks; the partner 8 dims are one more 16-byte
-//    load of the same qkv row). The rotated k is rounded to the cache dtype once and that
-//    value is both stored at t_b and scored against, so later steps that read the row back
-//    agree with this one.
+//    partial (m = -inf, l = 0); a guarded sequence gets zeros and no write. rot [2, B, D]
+//    (cos, sin) rotates the R q rows and the one new k row in registers (half-split rule inside
+//    each of rot_dims chunks; the partner 8 dims are one more 16-byte load of the same qkv
+//    row). The rotated k is rounded to the cache dtype once and that value is both stored at
+//    t_b and scored against, so later steps that read the row back agree with this one.
+//    R = 1 is built with and without EXT; R = 2, 4, 8 only with it, where null seq_lens / rot
+//    are runtime checks.
 #include "common.h"
 
 namespace pra {
@@ -33,15 +47,29 @@ namespace {
 
 constexpr int kWaves = 4;
 
+typedef float f2 __attribute__((ext_vector_type(2)));
+
+// v + (v of the lane that the DPP control selects): the cross-lane operand rides on the add
+// itself, so the R reductions per key cost VALU slots only and no LDS-pipe round trips
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v) {
+  return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+
+// sum over the G (8, 16 or 32) consecutive lanes of a key group, the same bits in every lane:
+// the two quad swaps, then the mirror inside each 8 and inside each 16 lanes
 template <int G>
 __device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = 1; o < G; o <<= 1) v += __shfl_xor(v, o, 64);
+  static_assert(G == 8 || G == 16 || G == 32, "key groups of 8, 16 or 32 lanes");
+  v = dpp_add<0xB1>(v);   // quad_perm [1, 0, 3, 2]
+  v = dpp_add<0x4E>(v);   // quad_perm [2, 3, 0, 1]
+  v = dpp_add<0x141>(v);  // row_half_mirror
+  if constexpr (G >= 16) v = dpp_add<0x140>(v);  // row_mirror
+  if constexpr (G == 32) v += __shfl_xor(v, 16, 64);
   return v;
 }
 
 // merge (m2, l2, a2) into (m, l, a)
-template <int N>
 __device__ __forceinline__ void merge(float& m, float& l, float* a, float m2, float l2, const float* a2) {
   const float M = fmaxf(m, m2);
   if (M == -INFINITY) return;
@@ -49,32 +77,30 @@ __device__ __forceinline__ void merge(float& m, float& l, float* a, float m2, fl
   const float c2 = (m2 == -INFINITY) ? 0.f : __expf(m2 - M);
   l = l * c1 + l2 * c2;
 #pragma unroll
-  for (int i = 0; i < N; ++i) a[i] = a[i] * c1 + a2[i] * c2;
+  for (int i = 0; i < 8; ++i) a[i] = a[i] * c1 + a2[i] * c2;
   m = M;
 }
 
-// x[8] (dims d0..d0+7 of one head row) rotated against its partner half a chunk away
+// x[8] (dims d0.. of one head row) rotated against its partner half a chunk away; c / s are
+// the lane's 8 cos / sin values, shared by every row the lane rotates
 template <typename T>
-__device__ __forceinline__ void rotate8(const T* row, int d0, int chunk, const float* cs, const float* sn, float* x) {
-  const int half = chunk >> 1;
-  const bool left = (d0 % chunk) < half;
-  float p[8], c[8], s[8];
+__device__ __forceinline__ void rotate8(const T* row, int d0, int half, bool left, const float* c, const float* s,
+                                        float* x) {
+  float p[8];
   load8<T>(row + (left ? d0 + half : d0 - half), p);
-  load8<float>(cs + d0, c);
-  load8<float>(sn + d0, s);
 #pragma unroll
   for (int i = 0; i < 8; ++i) x[i] = left ? x[i] * c[i] - p[i] * s[i] : x[i] * c[i] + p[i] * s[i];
 }
 
-template <typename T, int D, bool EXT>
+template <typename T, int D, int R, bool EXT>
 __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
-    const T* __restrict__ qkv,      // [B, 3, H, D] (bias already added)
-    T* __restrict__ cache,          // [2, B, H, L, D]
+    const T* __restrict__ qkv,      // [B, H + 2*KVH, D] (bias already added)
+    T* __restrict__ cache,          // [2, B, KVH, L, D]
     const float* __restrict__ mask, // [B, mask_len] additive, or null
     float* __restrict__ ws_ml,      // [B, H, S, 2]
     float* __restrict__ ws_acc,     // [B, H, S, D]
     T* __restrict__ out,            // [B, H, D] (used when splits == 1)
-    int B, int H, int L, int t_host, const int* __restrict__ t_dev, int keys_per_split, int mask_len,
+    int B, int KVH, int L, int t_host, const int* __restrict__ t_dev, int keys_per_split, int mask_len,
     float scale,
     const int* __restrict__ seq_lens,  // EXT: [B] per-sequence position, or null
     const float* __restrict__ rot,     // EXT: [2, B, D] cos then sin, or null
@@ -84,8 +110,10 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
   int t = t_dev ? t_dev[0] : t_host;
   constexpr int G = D / 8;            // lanes per key
   constexpr int KPW = 64 / G;         // keys per wave per sub-step
-  const int split = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+  static_assert(kWaves * KPW >= R, "one lane group per query head in the epilogue");
+  const int split = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z;
   const int splits = gridDim.x;
+  const int H = KVH * R, h0 = kvh * R;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int gl = lane % G, grp = lane / G;
   bool in_bound = true;
@@ -99,70 +127,75 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
   const int lo = split * keys_per_split;
   const int hi = t_ok ? min(t + 1, lo + keys_per_split) : lo;
 
-  const size_t BH = (size_t)B * H;
-  const T* qrow = qkv + ((size_t)b * 3 * H + h) * D;
-  const T* knew = qkv + ((size_t)b * 3 * H + H + h) * D;
-  const T* vnew = qkv + ((size_t)b * 3 * H + 2 * H + h) * D;
-  T* kc = cache + ((size_t)b * H + h) * (size_t)L * D;
-  T* vc = cache + (BH + (size_t)b * H + h) * (size_t)L * D;
+  const size_t rows = (size_t)H + 2 * KVH;
+  const T* qrow = qkv + ((size_t)b * rows + h0) * D;          // R consecutive query rows
+  const T* knew = qkv + ((size_t)b * rows + H + kvh) * D;
+  const T* vnew = knew + (size_t)KVH * D;
+  T* kc = cache + ((size_t)b * KVH + kvh) * (size_t)L * D;
+  T* vc = cache + (((size_t)B + b) * KVH + kvh) * (size_t)L * D;
+  const size_t w0 = ((size_t)b * H + h0) * splits + split;    // partial of query head h0; head r: + r*splits
 
-  float q[8];
-  float kt[8];  // EXT: the token's own k exactly as the cache holds it
-  if constexpr (EXT) {
-    if (hi <= lo) {  // a key range past t_b, or a guarded position: no loads, the empty partial
+  if (hi <= lo) {  // a key range past t, or a guarded position: no loads, R empty partials
+    if (splits == 1) {
       if (wave == 0 && grp == 0) {
-        if (splits == 1) {
-          const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-          store8<T>(out + ((size_t)b * H + h) * D + gl * 8, z);
-        } else if (gl == 0) {
-          *reinterpret_cast<float2*>(ws_ml + (((size_t)b * H + h) * splits + split) * 2) =
-              make_float2(-INFINITY, 0.f);
-        }
+        const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int r = 0; r < R; ++r) store8<T>(out + ((size_t)b * H + h0 + r) * D + gl * 8, z);
       }
-      return;
+    } else if (threadIdx.x < R) {
+      *reinterpret_cast<float2*>(ws_ml + (w0 + (size_t)threadIdx.x * splits) * 2) = make_float2(-INFINITY, 0.f);
     }
-    load8<T>(qrow + gl * 8, q);
-    load8<T>(knew + gl * 8, kt);
+    return;
+  }
+
+  float q[R][8];
+  float kt[8];  // the token's own k exactly as the cache holds it
+#pragma unroll
+  for (int r = 0; r < R; ++r) load8<T>(qrow + r * D + gl * 8, q[r]);
+  load8<T>(knew + gl * 8, kt);
+  if constexpr (EXT) {
     if (rot) {
-      const float* cs = rot + (size_t)b * D;
-      const float* sn = rot + ((size_t)B + b) * D;
-      rotate8<T>(qrow, gl * 8, D / rot_dims, cs, sn, q);
-      rotate8<T>(knew, gl * 8, D / rot_dims, cs, sn, kt);
+      const int chunk = D / rot_dims, half = chunk >> 1;
+      const bool left = ((gl * 8) % chunk) < half;
+      float c[8], s[8];
+      load8<float>(rot + (size_t)b * D + gl * 8, c);
+      load8<float>(rot + ((size_t)B + b) * D + gl * 8, s);
+#pragma unroll
+      for (int r = 0; r < R; ++r) rotate8<T>(qrow + r * D, gl * 8, half, left, c, s, q[r]);
+      rotate8<T>(knew, gl * 8, half, left, c, s, kt);
 #pragma unroll
       for (int i = 0; i < 8; ++i) kt[i] = Cvt<T>::to(Cvt<T>::from(kt[i]));  // rounded once
     }
-    if (t < hi && wave == 0 && grp == 0) {  // append the new token (here hi > lo, so t_ok and t >= lo)
-      float v[8];
-      store8<T>(kc + (size_t)t * D + gl * 8, kt);
-      load8<T>(vnew + gl * 8, v);
-      store8<T>(vc + (size_t)t * D + gl * 8, v);
-    }
-  } else {
-    if (t_ok && t >= lo && t < hi && wave == 0 && grp == 0) {  // append the new token to the cache
-      float kv[8];
-      load8<T>(knew + gl * 8, kv);
-      store8<T>(kc + (size_t)t * D + gl * 8, kv);
-      load8<T>(vnew + gl * 8, kv);
-      store8<T>(vc + (size_t)t * D + gl * 8, kv);
-    }
-    load8<T>(qrow + gl * 8, q);
+  }
+  if (t < hi && wave == 0 && grp == 0) {  // append the new token (hi > lo here, so t_ok and t >= lo)
+    float v[8];
+    store8<T>(kc + (size_t)t * D + gl * 8, kt);
+    load8<T>(vnew + gl * 8, v);
+    store8<T>(vc + (size_t)t * D + gl * 8, v);
   }
 #pragma unroll
-  for (int i = 0; i < 8; ++i) q[i] *= scale;
-
-  float m = -INFINITY, l = 0.f, acc[8];
+  for (int r = 0; r < R; ++r) {
 #pragma unroll
-  for (int i = 0; i < 8; ++i) acc[i] = 0.f;
+    for (int i = 0; i < 8; ++i) q[r][i] *= scale;
+  }
+
+  float m[R], l[R], acc[R][8];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    m[r] = -INFINITY;
+    l[r] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[r][i] = 0.f;
+  }
 
   const float* mrow = mask ? mask + (size_t)b * mask_len : nullptr;
   constexpr int STEP = kWaves * KPW * 2;
   for (int base = lo; base < hi; base += STEP) {
-    int key[2];
-    float kx[2][8], vx[2][8];
+    float kx[2][8], vx[2][8], add[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      key[u] = base + (u * kWaves + wave) * KPW + grp;
-      const int kk = key[u] < hi ? key[u] : lo;
+      const int key = base + (u * kWaves + wave) * KPW + grp;
+      const int kk = key < hi ? key : lo;
       const T* kp = (kk == t) ? knew : kc + (size_t)kk * D;
       const T* vp = (kk == t) ? vnew : vc + (size_t)kk * D;
       load8<T>(kp + gl * 8, kx[u]);
@@ -173,58 +206,76 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
           for (int i = 0; i < 8; ++i) kx[u][i] = kt[i];
         }
       }
+      // a key past the range scores -inf: its weight is exactly 0
+      add[u] = key < hi ? (mrow ? mrow[key] : 0.f) : -INFINITY;
     }
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      float s = 0.f;
+    for (int r = 0; r < R; ++r) {
+      f2 d0 = {0.f, 0.f}, d1 = {0.f, 0.f};  // packed fp32 FMAs: even and odd dims apart
 #pragma unroll
-      for (int i = 0; i < 8; ++i) s += q[i] * kx[u][i];
-      s = group_sum<G>(s);
-      if (key[u] >= hi) continue;
-      if (mrow) s += mrow[key[u]];
-      const float mn = fmaxf(m, s);
-      if (mn == -INFINITY) continue;  // fully masked so far
-      const float c = (m == -INFINITY) ? 0.f : __expf(m - mn);
-      const float p = __expf(s - mn);
-      l = l * c + p;
+      for (int i = 0; i < 8; i += 2) {
+        const f2 qq = {q[r][i], q[r][i + 1]};
+        d0 += qq * f2{kx[0][i], kx[0][i + 1]};
+        d1 += qq * f2{kx[1][i], kx[1][i + 1]};
+      }
+      float s0 = d0.x + d0.y, s1 = d1.x + d1.y;
+      s0 = group_sum<G>(s0) + add[0];
+      s1 = group_sum<G>(s1) + add[1];
+      const float mn = fmaxf(m[r], fmaxf(s0, s1));
+      const float ms = (mn == -INFINITY) ? 0.f : mn;  // fully masked so far: every weight below is 0
+      const float c = __expf(m[r] - ms);
+      const float p0 = __expf(s0 - ms), p1 = __expf(s1 - ms);
+      l[r] = l[r] * c + p0 + p1;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) acc[i] = acc[i] * c + p * vx[u][i];
-      m = mn;
+      for (int i = 0; i < 8; ++i) acc[r][i] = acc[r][i] * c + p0 * vx[0][i] + p1 * vx[1][i];
+      m[r] = mn;
     }
   }
 
   // merge the KPW key groups of this wave (lanes gl, gl+G, ...)
 #pragma unroll
   for (int o = G; o < 64; o <<= 1) {
-    const float m2 = __shfl_xor(m, o, 64), l2 = __shfl_xor(l, o, 64);
-    float a2[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) a2[i] = __shfl_xor(acc[i], o, 64);
-    merge<8>(m, l, acc, m2, l2, a2);
+    for (int r = 0; r < R; ++r) {
+      const float m2 = __shfl_xor(m[r], o, 64), l2 = __shfl_xor(l[r], o, 64);
+      float a2[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) a2[i] = __shfl_xor(acc[r][i], o, 64);
+      merge(m[r], l[r], acc[r], m2, l2, a2);
+    }
   }
-  // merge the waves through LDS
-  __shared__ float s_ml[kWaves][2];
-  __shared__ float s_acc[kWaves][D];
+  // merge the waves through LDS: every wave posts its R states, lane group r finishes head r
+  __shared__ float s_ml[kWaves][R][2];
+  __shared__ __attribute__((aligned(16))) float s_acc[kWaves][R][D];
   if (grp == 0) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) s_acc[wave][gl * 8 + i] = acc[i];
-    if (gl == 0) { s_ml[wave][0] = m; s_ml[wave][1] = l; }
+    for (int r = 0; r < R; ++r) {
+      *reinterpret_cast<float4*>(&s_acc[wave][r][gl * 8]) = make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
+      *reinterpret_cast<float4*>(&s_acc[wave][r][gl * 8 + 4]) =
+          make_float4(acc[r][4], acc[r][5], acc[r][6], acc[r][7]);
+      if (gl == 0) { s_ml[wave][r][0] = m[r]; s_ml[wave][r][1] = l[r]; }
+    }
   }
   __syncthreads();
-  if (wave != 0 || grp != 0) return;
-  for (int w = 1; w < kWaves; ++w) merge<8>(m, l, acc, s_ml[w][0], s_ml[w][1], &s_acc[w][gl * 8]);
+  const int r = wave * KPW + grp;  // this lane group's query head
+  if (r >= R) return;
+  float fm = s_ml[0][r][0], fl = s_ml[0][r][1], fa[8];
+  load8<float>(&s_acc[0][r][gl * 8], fa);
+  for (int w = 1; w < kWaves; ++w) {
+    float a2[8];
+    load8<float>(&s_acc[w][r][gl * 8], a2);
+    merge(fm, fl, fa, s_ml[w][r][0], s_ml[w][r][1], a2);
+  }
   if (splits == 1) {
-    const float inv = l > 0.f ? 1.f / l : 0.f;
+    const float inv = fl > 0.f ? 1.f / fl : 0.f;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) acc[i] *= inv;
-    store8<T>(out + ((size_t)b * H + h) * D + gl * 8, acc);
+    for (int i = 0; i < 8; ++i) fa[i] *= inv;
+    store8<T>(out + ((size_t)b * H + h0 + r) * D + gl * 8, fa);
     return;
   }
-  const size_t w = ((size_t)b * H + h) * splits + split;
-  float* wa = ws_acc + w * D + gl * 8;
-  *reinterpret_cast<float4*>(wa) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-  *reinterpret_cast<float4*>(wa + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);
-  if (gl == 0) *reinterpret_cast<float2*>(ws_ml + w * 2) = make_float2(m, l);
+  const size_t w = w0 + (size_t)r * splits;
+  store8<float>(ws_acc + w * D + gl * 8, fa);
+  if (gl == 0) *reinterpret_cast<float2*>(ws_ml + w * 2) = make_float2(fm, fl);
 }
 
 template <typename T, int D>
@@ -247,25 +298,55 @@ __global__ void __launch_bounds__(D) mmha_combine_k(const float* __restrict__ ws
   out[((size_t)b * H + h) * D + d] = Cvt<T>::from(den > 0.f ? num / den : 0.f);
 }
 
-template <typename T, int D>
-int launch(const void* qkv, void* cache, const float* mask, float* ws, void* out, int B, int H, int L, int t,
-           const int* t_dev, int splits, int mask_len, float scale, const int* seq_lens, const float* rot,
-           int rot_dims, hipStream_t s) {
-  const int keys = t_dev ? L : t + 1;  // device position: splits cover the whole cache
-  const int per = (keys + splits - 1) / splits;
-  float* ws_ml = ws;
-  float* ws_acc = ws + (((size_t)B * H * splits * 2 + 3) / 4) * 4;  // 16-B aligned
-  if (seq_lens || rot)
-    hipLaunchKernelGGL((mmha_split_k<T, D, true>), dim3(splits, H, B), dim3(kWaves * 64), 0, s, (const T*)qkv,
-                       (T*)cache, mask, ws_ml, ws_acc, (T*)out, B, H, L, t, t_dev, per, mask_len, scale, seq_lens, rot,
-                       rot_dims);
-  else
-    hipLaunchKernelGGL((mmha_split_k<T, D, false>), dim3(splits, H, B), dim3(kWaves * 64), 0, s, (const T*)qkv,
-                       (T*)cache, mask, ws_ml, ws_acc, (T*)out, B, H, L, t, t_dev, per, mask_len, scale, nullptr,
-                       nullptr, 0);
-  if (splits > 1)
-    hipLaunchKernelGGL((mmha_combine_k<T, D>), dim3(H, B), dim3(D), 0, s, ws_ml, ws_acc, (T*)out, splits);
+struct Args {
+  const void* qkv;
+  void* cache;
+  const float* mask;
+  float* ws;
+  void* out;
+  int B, H, KVH, L, t;
+  const int* t_dev;
+  int splits, mask_len;
+  float scale;
+  const int* seq_lens;
+  const float* rot;
+  int rot_dims;
+  hipStream_t s;
+};
+
+template <typename T, int D, int R, bool EXT>
+int launch(const Args& a) {
+  const int keys = a.t_dev ? a.L : a.t + 1;  // device position: splits cover the whole cache
+  const int per = (keys + a.splits - 1) / a.splits;
+  float* ws_ml = a.ws;
+  float* ws_acc = a.ws + (((size_t)a.B * a.H * a.splits * 2 + 3) / 4) * 4;  // 16-B aligned
+  hipLaunchKernelGGL((mmha_split_k<T, D, R, EXT>), dim3(a.splits, a.KVH, a.B), dim3(kWaves * 64), 0, a.s,
+                     (const T*)a.qkv, (T*)a.cache, a.mask, ws_ml, ws_acc, (T*)a.out, a.B, a.KVH, a.L, a.t, a.t_dev,
+                     per, a.mask_len, a.scale, a.seq_lens, a.rot, a.rot_dims);
+  if (a.splits > 1)
+    hipLaunchKernelGGL((mmha_combine_k<T, D>), dim3(a.H, a.B), dim3(D), 0, a.s, ws_ml, ws_acc, (T*)a.out, a.splits);
   return 0;
+}
+
+template <typename T, int D>
+int launch_r(const Args& a) {
+  switch (a.H / a.KVH) {
+    case 1: return (a.seq_lens || a.rot) ? launch<T, D, 1, true>(a) : launch<T, D, 1, false>(a);
+    case 2: return launch<T, D, 2, true>(a);
+    case 4: return launch<T, D, 4, true>(a);
+    case 8: return launch<T, D, 8, true>(a);
+    default: return -1;
+  }
+}
+
+template <typename T>
+int launch_d(int D, const Args& a) {
+  switch (D) {
+    case 64: return launch_r<T, 64>(a);
+    case 128: return launch_r<T, 128>(a);
+    case 256: return launch_r<T, 256>(a);
+    default: return -1;
+  }
 }
 
 }  // namespace
@@ -285,50 +366,22 @@ int pra_mmha_splits(int B, int H, int t) {
   return s;
 }
 
-// ws: fp32 workspace of B*H*splits*(2 + D) + 4 floats (unused when splits == 1).
-// seq_lens (device int32 [B]) and rot (device fp32 [2, B, D], rot_dims chunks) are optional: null
-// runs the plain kernel. t / t_dev stay the batch-wide bound that the splits were sized for.
-int pra_mmha_decode(const void* qkv, void* cache, const float* mask, float* ws, void* out, int B, int H, int L,
-                    int D, int t, const int* t_dev, int splits, int mask_len, float scale, int dt,
+// qkv [B, H + 2*KVH, D] (= [B, 3, H, D] when KVH = H), cache [2, B, KVH, L, D], R = H / KVH in
+// {1, 2, 4, 8}. splits come from pra_mmha_splits(B, KVH, t) (the workgroup count is
+// B*KVH*splits); ws: fp32 workspace of B*H*splits*(2 + D) + 4 floats (unused when splits == 1).
+// seq_lens (device int32 [B]) and rot (device fp32 [2, B, D], rot_dims chunks) are optional.
+// t / t_dev stay the batch-wide bound that the splits were sized for.
+int pra_mmha_decode(const void* qkv, void* cache, const float* mask, float* ws, void* out, int B, int H, int KVH,
+                    int L, int D, int t, const int* t_dev, int splits, int mask_len, float scale, int dt,
                     const int* seq_lens, const float* rot, int rot_dims, hipStream_t s) {
-  if (splits < 1) return -1;
+  if (splits < 1 || B < 1 || B > 65535 || KVH < 1 || KVH > 65535 || H < KVH || H % KVH != 0 || L < 1) return -1;
   if (!t_dev && (t < 0 || t >= L || (mask && mask_len < t + 1))) return -1;
   if (rot && (rot_dims < 1 || D % (16 * rot_dims) != 0)) return -1;  // a half chunk is whole 8-dim lanes
-#define PRA_MMHA(TT)                                                                                     \
-  switch (D) {                                                                                           \
-    case 64: return launch<TT, 64>(qkv, cache, mask, ws, out, B, H, L, t, t_dev, splits, mask_len, scale, \
-                                   seq_lens, rot, rot_dims, s);                                          \
-    case 128: return launch<TT, 128>(qkv, cache, mask, ws, out, B, H, L, t, t_dev, splits, mask_len, scale, \
-                                     seq_lens, rot, rot_dims, s);                                        \
-    case 256: return launch<TT, 256>(qkv, cache, mask, ws, out, B, H, L, t, t_dev, splits, mask_len, scale, \
-                                     seq_lens, rot, rot_dims, s);                                        \
-    default: return -1;                                                                                  \
-  }
-  if (dt == kBF16) { PRA_MMHA(bf16) }
-  if (dt == kF16) { PRA_MMHA(f16) }
-  if (dt == kF32) { PRA_MMHA(float) }
-#undef PRA_MMHA
-  return -1;
-}
-
-// the split merge alone, for split-K kernels in other files that fill the same workspace layout
-// (decode_attn_gqa.hip): ws_ml [B, H, splits, 2], ws_acc [B, H, splits, D] -> out [B, H, D]
-int pra_mmha_combine(const float* ws_ml, const float* ws_acc, void* out, int B, int H, int D, int splits, int dt,
-                     hipStream_t s) {
-#define PRA_COMBINE(TT)                                                                                      \
-  switch (D) {                                                                                               \
-    case 64: hipLaunchKernelGGL((mmha_combine_k<TT, 64>), dim3(H, B), dim3(64), 0, s, ws_ml, ws_acc, (TT*)out, \
-                                splits); return 0;                                                           \
-    case 128: hipLaunchKernelGGL((mmha_combine_k<TT, 128>), dim3(H, B), dim3(128), 0, s, ws_ml, ws_acc,       \
-                                 (TT*)out, splits); return 0;                                                \
-    case 256: hipLaunchKernelGGL((mmha_combine_k<TT, 256>), dim3(H, B), dim3(256), 0, s, ws_ml, ws_acc,       \
-                                 (TT*)out, splits); return 0;                                                \
-    default: return -1;                                                                                      \
-  }
-  if (dt == kBF16) { PRA_COMBINE(bf16) }
-  if (dt == kF16) { PRA_COMBINE(f16) }
-  if (dt == kF32) { PRA_COMBINE(float) }
-#undef PRA_COMBINE
+  const Args a{qkv, cache, mask, ws, out, B, H, KVH, L, t, t_dev, splits, mask_len, scale, seq_lens, rot,
+               rot_dims, s};
+  if (dt == kBF16) return launch_d<bf16>(D, a);
+  if (dt == kF16) return launch_d<f16>(D, a);
+  if (dt == kF32) return launch_d<float>(D, a);
   return -1;
 }
 }

@@ -763,8 +763,9 @@ def vocab_parallel_cross_entropy(logits, labels, pg=None, world=1, rank=0, ignor
 # Ragged batches: seq_lens [B] gives every sequence its own t_b (t stays the batch-wide upper
 # bound), rotary [2, B, D] (cos, sin) rotates q and the new k before anything else. A
 # sequence whose position is out of range gets a zero output and no cache write.
-# Grouped-query attention (decode_attn_gqa.hip): a 3-D qkv [B, H + 2*KVH, D] (query heads, then
-# k heads, then v heads) over a cache [2, B, KVH, L, D]; query head h reads K/V head h // (H/KVH).
+# Grouped-query attention (the same kernel template, H/KVH query rows per K/V row): a 3-D qkv
+# [B, H + 2*KVH, D] (query heads, then k heads, then v heads) over a cache [2, B, KVH, L, D];
+# query head h reads K/V head h // (H/KVH). The 4-D form is that row with KVH = H.
 # =============================================================================
 def _rotate_rows(x, cos, sin, dims):
     """Half-split rotation inside each of ``dims`` chunks: x [B, H, D] fp32, cos/sin [B, D]."""
@@ -830,8 +831,7 @@ def _mmha_ref(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0):
 
 @R.register_kernel('mmha_decode', 'hip', dtypes=_FLOATS)
 def _mmha_hip(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0):
-    gqa = qkv.dim() == 3            # [B, H + 2*KVH, D]: the grouped-query kernel (decode_attn_gqa.hip)
-    if gqa:
+    if qkv.dim() == 3:              # [B, H + 2*KVH, D]; the 4-D form is the same memory with KVH = H
         B, D, KVH = qkv.shape[0], qkv.shape[2], cache.shape[2]
         H = qkv.shape[1] - 2 * KVH
         if H // KVH not in GQA_RATIOS:
@@ -873,17 +873,10 @@ def _mmha_hip(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0):
         mlen = mask.shape[1]
         if t_dev is None and mlen < t + 1:
             raise ValueError(f"mmha_decode: mask covers {mlen} positions, need {t + 1}")
-    if gqa:
+    if H > KVH:
         R._STATS[('mmha_decode_gqa', 'hip')] += 1
-        _native.lib().mmha_gqa_decode(_ptr(qkv), _ptr(cache), _ptr(mask) if mask is not None else 0,
-                                      _ptr(ws), _ptr(out), B, H, KVH, L, D, int(t),
-                                      _ptr(t_dev) if t_dev is not None else 0, splits, mlen,
-                                      1.0 / math.sqrt(D), _dt(qkv), _stream(),
-                                      _ptr(seq_lens) if seq_lens is not None else 0,
-                                      _ptr(rotary) if rotary is not None else 0, int(rotary_dims))
-        return out
     _native.lib().mmha_decode(_ptr(qkv), _ptr(cache), _ptr(mask) if mask is not None else 0,
-                              _ptr(ws), _ptr(out), B, H, L, D, int(t),
+                              _ptr(ws), _ptr(out), B, H, KVH, L, D, int(t),
                               _ptr(t_dev) if t_dev is not None else 0, splits, mlen,
                               1.0 / math.sqrt(D), _dt(qkv), _stream(),
                               _ptr(seq_lens) if seq_lens is not None else 0,

@@ -370,6 +370,125 @@ def test_gqa_unsupported_ratio_raises_gpu():
     assert float(cache.abs().sum()) == 0.0
 
 
+# ----------------------------------------------------------------------------- one kernel, R = 1 too
+# f16 against 'ref'. 'ref' computes in fp32 and rounds its result to f16 once, half an ulp or
+# 2^-11 = 4.9e-4 relative; test_ref_in_f16_is_inside_the_f16_tolerance_of_float64 holds it to
+# this bound against float64 on the CPU, so no wider power of ten was needed.
+_TOL_F16 = 2e-3
+
+#                     H  KVH lens      mask and rotary
+_STEP = {'r1_plain': (4, 4, None, False),
+         'r1_ragged': (4, 4, (5, 257), True),
+         'r4_ragged': (8, 2, (5, 257), True)}
+
+
+def _step(name, D, dtype, device='cpu'):
+    """One decode step at B = 2, L = 300, time_step = 257: five splits of 52 keys, which is no
+    multiple of the keys a workgroup takes per iteration (64 at D = 64, 32 at D = 128).
+    Returns qkv (4-D when KVH = H), cache, time_step, mask and the keyword arguments."""
+    H, KVH, lens, ext = _STEP[name]
+    B, L, t = 2, 300, 257
+    g = torch.Generator().manual_seed(D + H)
+    qkv = torch.randn(B, H + 2 * KVH, D, generator=g).to(dtype).to(device)
+    cache = torch.randn(2, B, KVH, L, D, generator=g).to(dtype).to(device)
+    mask, kw = None, {}
+    if ext:
+        mask = torch.zeros(B, t + 1 + 3)
+        mask[:, ::7] = float('-inf')
+        for b, n in enumerate(lens):
+            mask[b, n] = 0.0
+        mask = mask.to(device)
+        ang = torch.rand(B, D, generator=g) * (2 * np.pi)
+        kw = dict(seq_lens=torch.tensor(lens, dtype=torch.int32).to(device),
+                  rotary=torch.stack([ang.cos(), ang.sin()]).to(device), rotary_dims=1)
+    if H == KVH:
+        qkv = qkv.reshape(B, 3, H, D)
+    return qkv, cache, t, mask, kw
+
+
+def _f64(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0):
+    """The step in float64; only the rotated new k is rounded to the cache dtype, as cached."""
+    B, KVH, D = qkv.shape[0], cache.shape[2], qkv.shape[-1]
+    row = qkv.reshape(B, -1, D).double()
+    H = row.shape[1] - 2 * KVH
+    q, k, v = row[:, :H], row[:, H:H + KVH], row[:, H + KVH:]
+    if rotary is not None:
+        cos, sin = rotary.double()
+        q, k = K._rotate_rows(q, cos, sin, rotary_dims), K._rotate_rows(k, cos, sin, rotary_dims)
+    k = k.to(qkv.dtype).double()
+    out = torch.zeros(B, H, D, dtype=torch.float64)
+    for b in range(B):
+        n = t if seq_lens is None else int(seq_lens[b])
+        K_ = torch.cat([cache[0, b, :, :n].double(), k[b][:, None]], 1).repeat_interleave(H // KVH, 0)
+        V_ = torch.cat([cache[1, b, :, :n].double(), v[b][:, None]], 1).repeat_interleave(H // KVH, 0)
+        s = torch.einsum('hd,hld->hl', q[b], K_) / np.sqrt(D)
+        if mask is not None:
+            s = s + mask[b, None, :n + 1].double()
+        out[b] = torch.einsum('hl,hld->hd', torch.softmax(s, -1), V_)
+    return out
+
+
+@pytest.mark.parametrize('D', [64, 128])
+@pytest.mark.parametrize('name', list(_STEP))
+def test_ref_in_f16_is_inside_the_f16_tolerance_of_float64(name, D):
+    qkv, cache, t, mask, kw = _step(name, D, torch.float16)
+    ref = R.get_kernel('mmha_decode', 'ref')(qkv, cache.clone(), t, mask, **kw)
+    torch.testing.assert_close(ref.double(), _f64(qkv, cache, t, mask, **kw), rtol=_TOL_F16, atol=_TOL_F16)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('D', [64, 128])
+@pytest.mark.parametrize('name', list(_STEP))
+def test_f16_hip_kernel_gpu(name, D):
+    qkv, cache, t, mask, kw = _step(name, D, torch.float16, 'cuda')
+    orig, c_ref = cache.clone(), cache.clone()
+    ref = R.get_kernel('mmha_decode', 'ref')(qkv, c_ref, t, mask, **kw)
+    out = K.mmha_decode(qkv, cache, t, mask, **kw)
+    torch.testing.assert_close(out.float(), ref.float(), rtol=_TOL_F16, atol=_TOL_F16)
+    torch.testing.assert_close(cache, c_ref)       # a rotated row may differ by one rounding
+    assert not torch.equal(cache, orig)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('D', [64, 128])
+@pytest.mark.parametrize('name', ['r1_plain', 'r1_ragged'])
+def test_3d_and_4d_forms_agree_gpu(name, D):
+    qkv4, cache, t, mask, kw = _step(name, D, torch.bfloat16, 'cuda')
+    B, _, H, _ = qkv4.shape
+    c3, c4 = cache.clone(), cache.clone()
+    before = R.stats().get(('mmha_decode_gqa', 'hip'), 0)
+    out3 = K.mmha_decode(qkv4.reshape(B, 3 * H, D), c3, t, mask, **kw)
+    out4 = K.mmha_decode(qkv4, c4, t, mask, **kw)
+    assert torch.equal(out3, out4) and torch.equal(c3, c4)
+    assert not torch.equal(c3, cache)
+    assert R.stats().get(('mmha_decode_gqa', 'hip'), 0) == before    # KVH = H is not grouped
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('D', [64, 128])
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float32])
+def test_r1_split_boundaries_with_device_step_gpu(D, dtype):
+    # a device time_step: five splits of 60 keys cover L = 300. Sequence 0 is at t = 0 (one key
+    # of weight exactly 1 in split 0, four empty partials), sequence 1 in the last cache slot.
+    B, H, L, lens = 2, 4, 300, (0, 299)
+    g = torch.Generator().manual_seed(D)
+    qkv = torch.randn(B, 3, H, D, generator=g).to(dtype).cuda()
+    cache = torch.randn(2, B, H, L, D, generator=g).to(dtype).cuda()
+    orig, c_ref = cache.clone(), cache.clone()
+    t = torch.tensor([L - 1], dtype=torch.int32).cuda()
+    sl = torch.tensor(lens, dtype=torch.int32).cuda()
+    ref = R.get_kernel('mmha_decode', 'ref')(qkv, c_ref, t, None, seq_lens=sl)
+    out = K.mmha_decode(qkv, cache, t, seq_lens=sl)
+    assert torch.equal(out[0], ref[0]) and torch.equal(out[0], qkv[0, 2])
+    tol = _TOL[dtype]
+    torch.testing.assert_close(out[1].float(), ref[1].float(), rtol=tol, atol=tol)
+    assert torch.equal(cache, c_ref)
+    for b, n in enumerate(lens):                   # the appended rows, and no other row changed
+        assert torch.equal(cache[0, b, :, n], qkv[b, 1]) and torch.equal(cache[1, b, :, n], qkv[b, 2])
+        cache[:, b, :, n] = orig[:, b, :, n]
+    assert torch.equal(cache, orig)
+
+
 # ----------------------------------------------------------------------------- GPU: end to end
 _BIG = dict(E=512, H=4, KVH=2)                       # head dim 128
 
