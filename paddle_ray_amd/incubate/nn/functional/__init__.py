@@ -217,7 +217,10 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
                             cache_kvs=None, pre_caches=None, seq_lens=None, rotary_embs=None,
                             time_step=None, attn_mask=None, dropout_rate=0.0, rotary_emb_dims=0,
                             activation="gelu", training=False, mode='upscale_in_train',
-                            trans_qkvw=True, ring_id=-1, name=None, gqa_group_size=-1):
+                            trans_qkvw=True, ring_id=-1, name=None, gqa_group_size=-1,
+                            cache_k_quant_scales=None, cache_v_quant_scales=None,
+                            cache_k_dequant_scales=None, cache_v_dequant_scales=None,
+                            quant_round_type=1, quant_max_bound=127.0, quant_min_bound=-127.0):
     """N transformer layers for inference / generation (parity: reference
     incubate/nn/functional/fused_transformer.py:872 and fused_multi_transformer_op.cu.h).
 
@@ -239,6 +242,13 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
       K/V head ``h // (H // KVH)``. The decode phase hands the row to the grouped-query HIP
       kernel, which streams every cached K/V row once for its H / KVH query heads; the context
       phase expands K/V over heads for the flash / SDPA call and caches the KVH heads.
+    * 8-bit KV cache: a ``uint8`` ``cache_kvs[i]`` goes with ``cache_k_quant_scales[i]`` and
+      ``cache_v_quant_scales[i]`` (per-layer lists of fp32 [KVH] tensors, or [B, KVH] for
+      per-sequence "dynamic" scales; the ``*_dequant_scales`` default to their reciprocals) and
+      ``quant_round_type`` / ``quant_max_bound`` / ``quant_min_bound`` (``ops.fused.kv_quantize``).
+      The context phase stores the quantised K/V of the prompt, any ``pre_caches`` prefix
+      included, while its own attention uses the unquantised K/V; the decode phase hands the
+      scales to the decode kernel, which reads the bytes and appends the quantised token.
     * every residual add + dropout + following LayerNorm is ONE add_dropout_layer_norm
       kernel; FFN1 runs with its bias+activation in the GEMM epilogue.
     Returns ``out`` or ``(out, cache_kvs)`` when caches are given (updated in place)."""
@@ -299,11 +309,22 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
         if KVH and cache is not None and (cache.dim() != 5 or cache.shape[2] != KVH):
             raise ValueError(f"fused_multi_transformer: cache {i} is {tuple(cache.shape)}, "
                              f"gqa_group_size={KVH} needs [2, B, {KVH}, max_len, D]")
+        qkw = {}
+        if cache is not None and (cache.dtype == torch.uint8 or any(
+                s is not None for s in (cache_k_quant_scales, cache_v_quant_scales,
+                                        cache_k_dequant_scales, cache_v_dequant_scales))):
+            qkw = dict(quant_round_type=quant_round_type, quant_max_bound=quant_max_bound,
+                       quant_min_bound=quant_min_bound)
+            for name, lst in (('cache_k_quant_scales', cache_k_quant_scales),
+                              ('cache_v_quant_scales', cache_v_quant_scales),
+                              ('cache_k_dequant_scales', cache_k_dequant_scales),
+                              ('cache_v_dequant_scales', cache_v_dequant_scales)):
+                qkw[name] = _t(lst[i]) if lst is not None else None
         if decode:
             if cache is None:
                 raise ValueError("fused_multi_transformer: time_step needs cache_kvs")
             o = K.mmha_decode(qkv[:, 0].contiguous(), cache, t, mask, seq_lens=sl, rotary=krot,
-                              rotary_dims=rotary_emb_dims if krot is not None else 0
+                              rotary_dims=rotary_emb_dims if krot is not None else 0, **qkw
                               ).reshape(B, 1, H * D)
         else:
             if KVH:
@@ -316,7 +337,14 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
                 P = pc.shape[3]
                 k = torch.cat([pc[0].transpose(1, 2).to(k.dtype), k], 1)
                 v = torch.cat([pc[1].transpose(1, 2).to(v.dtype), v], 1)
-            if cache is not None:
+            quant = K._kv_quant_args(B, cache, qkw['cache_k_quant_scales'], qkw['cache_v_quant_scales'],
+                                     qkw['cache_k_dequant_scales'], qkw['cache_v_dequant_scales'],
+                                     quant_round_type, quant_max_bound, quant_min_bound,
+                                     h.device) if qkw else None
+            if quant is not None:                    # the bytes the decode kernel reads back
+                cache[0, :, :, :P + S] = K.kv_quantize(k.transpose(1, 2), quant[0][0], *quant[2:])
+                cache[1, :, :, :P + S] = K.kv_quantize(v.transpose(1, 2), quant[0][1], *quant[2:])
+            elif cache is not None:
                 cache[0, :, :, :P + S] = k.transpose(1, 2)
                 cache[1, :, :, :P + S] = v.transpose(1, 2)
             if KVH and H != KVH:                     # the cache keeps KVH heads; attention sees H

@@ -139,7 +139,11 @@ class FusedMultiTransformer(Layer):
     ``gqa_group_size`` = KVH > 0 is grouped-query attention with KVH K/V heads
     (``self.kv_num_heads``), each shared by ``num_heads / KVH`` query heads: qkv is
     [H + 2*KVH, D, E] (query heads, k heads, v heads), its bias [H + 2*KVH, D], and the caches
-    are [2, B, KVH, max_len, D]."""
+    are [2, B, KVH, max_len, D].
+    ``uint8`` caches are the 8-bit KV cache: ``forward`` then takes the per-layer lists
+    ``cache_k_quant_scales`` / ``cache_v_quant_scales`` (fp32 [KVH], or [B, KVH] per sequence;
+    optional ``cache_*_dequant_scales``) and ``quant_round_type`` / ``quant_max_bound`` /
+    ``quant_min_bound``, as ``fused_multi_transformer`` does."""
 
     def __init__(self, embed_dim, num_heads, dim_feedforward, dropout_rate=0.0, activation="gelu",
                  normalize_before=True, ln_scale_attrs=None, ln_bias_attrs=None,
@@ -198,7 +202,9 @@ class FusedMultiTransformer(Layer):
                 getattr(self, n).append(p)
 
     def forward(self, src, attn_mask=None, caches=None, pre_caches=None, rotary_embs=None,
-                rotary_emb_dims=0, seq_lens=None, time_step=None):
+                rotary_emb_dims=0, seq_lens=None, time_step=None, cache_k_quant_scales=None,
+                cache_v_quant_scales=None, cache_k_dequant_scales=None, cache_v_dequant_scales=None,
+                quant_round_type=1, quant_max_bound=127.0, quant_min_bound=-127.0):
         return FF.fused_multi_transformer(
             src, self.ln_scales, self.ln_biases, self.qkv_weights, self.qkv_biases,
             self.linear_weights, self.linear_biases, self.ffn_ln_scales, self.ffn_ln_biases,
@@ -207,7 +213,11 @@ class FusedMultiTransformer(Layer):
             pre_caches=pre_caches, seq_lens=seq_lens, rotary_embs=rotary_embs,
             time_step=time_step, attn_mask=attn_mask, dropout_rate=self.dropout_rate,
             rotary_emb_dims=rotary_emb_dims, activation=self.activation, training=self.training,
-            trans_qkvw=self._trans_qkvw, gqa_group_size=self._gqa_group_size)
+            trans_qkvw=self._trans_qkvw, gqa_group_size=self._gqa_group_size,
+            cache_k_quant_scales=cache_k_quant_scales, cache_v_quant_scales=cache_v_quant_scales,
+            cache_k_dequant_scales=cache_k_dequant_scales,
+            cache_v_dequant_scales=cache_v_dequant_scales, quant_round_type=quant_round_type,
+            quant_max_bound=quant_max_bound, quant_min_bound=quant_min_bound)
 
 
 class FusedMultiTransformerDecoder:
@@ -228,9 +238,21 @@ class FusedMultiTransformerDecoder:
     only its own part of the cache.
     ``set_rotary(cos, sin, rotary_emb_dims)`` installs [max_seq_len, D] rotary tables: prefill
     uses rows [0, S0), each step gathers every sequence's row by its current position.
+
+    8-bit KV cache: ``kv_cache_dtype='int8'`` allocates ``uint8`` caches (half the bytes a
+    bf16 cache streams per step and occupies per context; ``ops.fused.kv_quantize`` is the
+    stored byte). ``cache_scales`` is a per-layer list of ``(k_quant, v_quant)`` fp32 [KVH]
+    tensors, the static scales. With ``cache_scales=None`` the scales are dynamic: ``prefill``
+    sets, per layer, sequence and K/V head, ``127 / absmax`` over the sequence's own valid
+    prompt positions of K (after rotary) and of V (1 for an all-zero head); tokens decoded
+    later saturate at the bounds. Either way the scales live in persistent device buffers
+    (``self.kv_scales``, per layer fp32 [4, Bs, KVH] = k quant, v quant, k dequant, v dequant)
+    that ``prefill`` fills before the graph is captured, so the one graph keeps serving every
+    step. A dynamic ``prefill`` holds the prompt's K/V in the model dtype until it has the scales.
     """
 
-    def __init__(self, model, batch_size, max_seq_len, use_graph=True):
+    def __init__(self, model, batch_size, max_seq_len, use_graph=True, kv_cache_dtype=None,
+                 cache_scales=None):
         import torch
         self.model = model
         self.B, self.L = int(batch_size), int(max_seq_len)
@@ -239,7 +261,40 @@ class FusedMultiTransformerDecoder:
         D, E = model.head_dim, model.embed_dim
         KVH = getattr(model, 'kv_num_heads', model.num_heads)    # grouped-query models cache KVH heads
         n = len(model.qkv_weights)
-        self.caches = [torch.zeros(2, self.B, KVH, self.L, D, device=self.dev, dtype=self.dtype)
+        if kv_cache_dtype not in (None, 'int8'):
+            raise ValueError(f"FusedMultiTransformerDecoder: kv_cache_dtype must be None (the model "
+                             f"dtype) or 'int8', got {kv_cache_dtype!r}")
+        self.q8 = kv_cache_dtype == 'int8'
+        if cache_scales is not None and not self.q8:
+            raise ValueError("FusedMultiTransformerDecoder: cache_scales go with kv_cache_dtype='int8'")
+        self.dynamic_scales = self.q8 and cache_scales is None
+        self.kv_scales, self._qkw = None, {}
+        if self.q8:
+            Bs = self.B if self.dynamic_scales else 1
+            self.kv_scales = [torch.ones(4, Bs, KVH, device=self.dev, dtype=torch.float32)
+                              for _ in range(n)]
+            if cache_scales is not None:
+                if len(cache_scales) != n:
+                    raise ValueError(f"FusedMultiTransformerDecoder: cache_scales has "
+                                     f"{len(cache_scales)} entries for {n} layers")
+                for s, pair in zip(self.kv_scales, cache_scales):
+                    for j, q in enumerate(pair):
+                        q = torch.as_tensor(q._t if hasattr(q, '_t') else q, dtype=torch.float32)
+                        if tuple(q.shape) != (KVH,) or not bool((torch.isfinite(q) & (q > 0)).all()):
+                            raise ValueError(f"FusedMultiTransformerDecoder: cache_scales holds per "
+                                             f"layer (k_quant, v_quant), finite positive [{KVH}] "
+                                             f"tensors; got {tuple(q.shape)}")
+                        s[j, 0].copy_(q)
+                        s[2 + j, 0].copy_(1.0 / q.to(self.dev))
+            # views of the packed buffers: the decode wrapper finds them packed and copies nothing
+            pick = (lambda s, j: s[j]) if self.dynamic_scales else (lambda s, j: s[j, 0])
+            self._qkw = {name: [pick(s, j) for s in self.kv_scales] for j, name in enumerate(
+                ('cache_k_quant_scales', 'cache_v_quant_scales', 'cache_k_dequant_scales',
+                 'cache_v_dequant_scales'))}
+        # a uint8 cache starts at the byte of level 0
+        self.caches = [torch.full((2, self.B, KVH, self.L, D), 128, device=self.dev, dtype=torch.uint8)
+                       if self.q8 else
+                       torch.zeros(2, self.B, KVH, self.L, D, device=self.dev, dtype=self.dtype)
                        for _ in range(n)]
         self.t = torch.zeros(1, dtype=torch.int32, device=self.dev)
         self.lens = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
@@ -293,7 +348,17 @@ class FusedMultiTransformerDecoder:
             sl = sl.reshape(self.B).to(device=self.dev, dtype=torch.int32)
             kw['seq_lens'] = Tensor(sl)
         with torch.no_grad():
-            out, _ = self.model(Tensor(xt), attn_mask=attn_mask, caches=self._caches(), **kw)
+            if self.dynamic_scales:
+                # the prompt's K/V in the model dtype first: their absmax gives the scales
+                KVH, D = self.caches[0].shape[2], self.caches[0].shape[4]
+                tmp = [torch.zeros(2, self.B, KVH, S0, D, device=self.dev, dtype=self.dtype)
+                       for _ in self.caches]
+                out, _ = self.model(Tensor(xt), attn_mask=attn_mask, caches=[Tensor(c) for c in tmp],
+                                    **kw)
+                self._quantize_prompt(tmp, sl if ragged else None)
+            else:
+                out, _ = self.model(Tensor(xt), attn_mask=attn_mask, caches=self._caches(), **kw,
+                                    **self._qkw)
         if ragged:
             self.lens.copy_(sl)
             self.t.copy_(sl.max().reshape(1))
@@ -304,9 +369,31 @@ class FusedMultiTransformerDecoder:
             self.ragged, self._graph = ragged, None      # the other graph
         return out
 
+    def _quantize_prompt(self, kv, seq_lens):
+        """Dynamic scales from the prompt's K/V (``kv``: per layer [2, B, KVH, S0, D], K after
+        rotary) over each sequence's valid positions, written into ``self.kv_scales``; then
+        the quantised prompt into the uint8 caches."""
+        import torch
+        from ...ops import fused as K
+        S0 = kv[0].shape[3]
+        pad = None
+        if seq_lens is not None:
+            pad = (torch.arange(S0, device=self.dev)[None, :] >= seq_lens[:, None].to(self.dev))
+            pad = pad[None, :, None, :, None]
+        for s, c, x in zip(self.kv_scales, self.caches, kv):
+            a = x.float().abs()
+            if pad is not None:
+                a = a.masked_fill(pad, 0.0)
+            a = a.amax(dim=(3, 4))                            # [2, B, KVH]
+            q = torch.where(a > 0, 127.0 / a, torch.ones_like(a))
+            s[:2].copy_(q)
+            s[2:].copy_(1.0 / q)
+            c[0, :, :, :S0] = K.kv_quantize(x[0], s[0])
+            c[1, :, :, :S0] = K.kv_quantize(x[1], s[1])
+
     def _step_eager(self):
         from ...framework.core import Tensor
-        kw = {}
+        kw = dict(self._qkw)
         if self.ragged:
             kw['seq_lens'] = Tensor(self.lens)
         if self.rot is not None:

@@ -33,7 +33,8 @@ void pra_vp_ce_bwd(const void*, const int64_t*, const float*, const float*, void
 const char* pra_build_info();
 int pra_mmha_splits(int, int, int);
 int pra_mmha_decode(const void*, void*, const float*, float*, void*, int, int, int, int, int, int, const int*, int,
-                    int, float, int, const int*, const float*, int, hipStream_t);
+                    int, float, int, const int*, const float*, int, hipStream_t, int, const float*, int, int, float,
+                    float);
 void pra_bias_gelu_fwd(const void*, const void*, void*, int64_t, int, int, int, hipStream_t);
 void pra_bias_gelu_bwd(const void*, const void*, const void*, void*, int64_t, int, int, int, hipStream_t);
 void pra_adamw_mt(const int64_t*, const float*, const int64_t*, int, float, float, float, float, float, float, float,
@@ -269,9 +270,24 @@ PYBIND11_MODULE(_pra_hip, m) {
                           int splits, int mask_len, float scale, int dt, P s, P seq_lens, P rot, int rot_dims) {
     if (pra_mmha_decode(CV(qkv), V(cache), CF(mask), F(ws), V(out), B, H, KVH, L, D, t,
                         reinterpret_cast<const int*>(t_dev), splits, mask_len, scale, dt,
-                        reinterpret_cast<const int*>(seq_lens), CF(rot), rot_dims, S(s)) != 0)
+                        reinterpret_cast<const int*>(seq_lens), CF(rot), rot_dims, S(s), dt, nullptr, 0, 1, 127.f,
+                        -127.f) != 0)
       throw std::invalid_argument(
           "mmha_decode: unsupported head_dim/group ratio/dtype/rotary_dims or time_step out of range");
+    check_launch("mmha_decode");
+  });
+  // the same entry over a uint8 cache (cache dtype code 3): scales is the packed fp32 [4, Bs, KVH]
+  m.def("mmha_decode_q8", [](P qkv, P cache, P mask, P ws, P out, int B, int H, int KVH, int L, int D, int t,
+                             P t_dev, int splits, int mask_len, float scale, int dt, P s, P seq_lens, P rot,
+                             int rot_dims, P scales, int scale_batch_stride, int round_type, float qmax,
+                             float qmin) {
+    if (pra_mmha_decode(CV(qkv), V(cache), CF(mask), F(ws), V(out), B, H, KVH, L, D, t,
+                        reinterpret_cast<const int*>(t_dev), splits, mask_len, scale, dt,
+                        reinterpret_cast<const int*>(seq_lens), CF(rot), rot_dims, S(s), 3, CF(scales),
+                        scale_batch_stride, round_type, qmax, qmin) != 0)
+      throw std::invalid_argument(
+          "mmha_decode: unsupported head_dim/group ratio/dtype/rotary_dims/quantisation arguments for a uint8 "
+          "cache, or time_step out of range");
     check_launch("mmha_decode");
   });
   m.def("bias_gelu_fwd", [](P x, P b, P y, int64_t rows, int cols, int dt, int approx, P s) {

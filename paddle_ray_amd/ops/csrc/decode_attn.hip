@@ -40,12 +40,28 @@
 //    t_b and scored against, so later steps that read the row back agree with this one.
 //    R = 1 is built with and without EXT; R = 2, 4, 8 only with it, where null seq_lens / rot
 //    are runtime checks.
+//  * 8-bit cache (Q8 instantiations, always EXT; a float-cache one is compiled without any of
+//    it): the cache is uint8, a byte u holding the level u - 128 =
+//    clamp(round(x * quant_scale), qmin, qmax), read back as (u - 128) * dequant_scale, with
+//    fp32 scales per K/V head ([4, Bs, KVH]: k quant, v quant, k dequant, v dequant; Bs = 1 or
+//    B). A lane keeps its 8 dims, now one 8-byte load per row, and takes four keys per
+//    iteration instead of two so as many bytes stay in flight; the rows stay raw (uint2) until
+//    used and a byte becomes a float with v_cvt_f32_ubyte0..3. Scales and the offset cost
+//    nothing per element: k dequant is folded into the scaled q rows and the offset into one
+//    constant per query row, s = q'.u - 128 * sum(q'); V accumulates the raw bytes and the
+//    epilogue applies (acc - 128 * l) * v dequant before the partial is posted, so the
+//    workspace and mmha_combine_k see ordinary partials. The new token's K (rotated in fp32,
+//    not rounded to T) and V are quantised in registers with one fp32 multiply and one
+//    rounding, appended as one 8-byte vector store per lane, and scored as those levels.
+#include <type_traits>
+
 #include "common.h"
 
 namespace pra {
 namespace {
 
 constexpr int kWaves = 4;
+constexpr int kCacheU8 = 3;  // cache dtype code of the 8-bit cache (the float ones are DType)
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -92,10 +108,50 @@ __device__ __forceinline__ void rotate8(const T* row, int d0, int half, bool lef
   for (int i = 0; i < 8; ++i) x[i] = left ? x[i] * c[i] - p[i] * s[i] : x[i] * c[i] + p[i] * s[i];
 }
 
-template <typename T, int D, int R, bool EXT>
+// what only a Q8 instantiation is given (an empty parameter otherwise)
+template <bool Q8> struct QParams {};
+template <> struct QParams<true> {
+  const float* scales;  // [4, Bs, KVH] fp32: k quant, v quant, k dequant, v dequant
+  int bstride;          // 0 (Bs = 1) or KVH (Bs = B)
+  int round_type;       // 1: half away from zero, 0: half to even
+  float qmax, qmin;     // level bounds, -128 <= qmin < qmax <= 127
+};
+
+// 8 values -> 8 stored bytes: level = clamp(round(x * qs)), byte = level + 128. One fp32
+// multiply, then the rounding; contraction is off so that the product is rounded before it
+// is used, exactly as x * qs is in torch
+__device__ __forceinline__ uint2 quant8(const float* x, float qs, int round_type, float qmax, float qmin) {
+#pragma clang fp contract(off)
+  uint32_t w[2] = {0u, 0u};
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const float y = x[i] * qs;
+    float r;
+    if (round_type == 0) {
+      r = rintf(y);
+    } else {  // y - trunc(y) is exact
+      const float tr = truncf(y);
+      r = tr + (fabsf(y - tr) >= 0.5f ? copysignf(1.f, y) : 0.f);
+    }
+    r = fminf(fmaxf(r, qmin), qmax);
+    w[i >> 2] |= (uint32_t)((int)r + 128) << (8 * (i & 3));
+  }
+  return make_uint2(w[0], w[1]);
+}
+
+// 8 stored bytes -> 8 floats in [0, 255] (v_cvt_f32_ubyte0..3); the offset is applied elsewhere
+__device__ __forceinline__ void unpack8(uint2 w, float* o) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    o[i] = (float)((w.x >> (8 * i)) & 0xffu);
+    o[4 + i] = (float)((w.y >> (8 * i)) & 0xffu);
+  }
+}
+
+template <typename T, int D, int R, bool EXT, bool Q8>
 __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
     const T* __restrict__ qkv,      // [B, H + 2*KVH, D] (bias already added)
-    T* __restrict__ cache,          // [2, B, KVH, L, D]
+    std::conditional_t<Q8, uint8_t, T>* __restrict__ cache,  // [2, B, KVH, L, D]
     const float* __restrict__ mask, // [B, mask_len] additive, or null
     float* __restrict__ ws_ml,      // [B, H, S, 2]
     float* __restrict__ ws_acc,     // [B, H, S, D]
@@ -104,7 +160,9 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
     float scale,
     const int* __restrict__ seq_lens,  // EXT: [B] per-sequence position, or null
     const float* __restrict__ rot,     // EXT: [2, B, D] cos then sin, or null
-    int rot_dims) {
+    int rot_dims, QParams<Q8> qp) {
+  static_assert(EXT || !Q8, "the Q8 instantiations are EXT ones");
+  using C = std::conditional_t<Q8, uint8_t, T>;  // a cache element
   // t_dev (HIP-graph decode loops): the position comes from device memory, so one captured
   // graph serves every step; an out-of-range position writes nothing and outputs zeros
   int t = t_dev ? t_dev[0] : t_host;
@@ -131,8 +189,8 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
   const T* qrow = qkv + ((size_t)b * rows + h0) * D;          // R consecutive query rows
   const T* knew = qkv + ((size_t)b * rows + H + kvh) * D;
   const T* vnew = knew + (size_t)KVH * D;
-  T* kc = cache + ((size_t)b * KVH + kvh) * (size_t)L * D;
-  T* vc = cache + (((size_t)B + b) * KVH + kvh) * (size_t)L * D;
+  C* kc = cache + ((size_t)b * KVH + kvh) * (size_t)L * D;
+  C* vc = cache + (((size_t)B + b) * KVH + kvh) * (size_t)L * D;
   const size_t w0 = ((size_t)b * H + h0) * splits + split;    // partial of query head h0; head r: + r*splits
 
   if (hi <= lo) {  // a key range past t, or a guarded position: no loads, R empty partials
@@ -163,11 +221,29 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
 #pragma unroll
       for (int r = 0; r < R; ++r) rotate8<T>(qrow + r * D, gl * 8, half, left, c, s, q[r]);
       rotate8<T>(knew, gl * 8, half, left, c, s, kt);
+      if constexpr (!Q8) {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) kt[i] = Cvt<T>::to(Cvt<T>::from(kt[i]));  // rounded once
+        for (int i = 0; i < 8; ++i) kt[i] = Cvt<T>::to(Cvt<T>::from(kt[i]));  // rounded once
+      }
     }
   }
-  if (t < hi && wave == 0 && grp == 0) {  // append the new token (hi > lo here, so t_ok and t >= lo)
+  float qscale = scale;
+  [[maybe_unused]] float vdq = 1.f;
+  [[maybe_unused]] uint2 ktq, vtq;  // Q8: the token's own k / v as the bytes the cache holds
+  if constexpr (Q8) {
+    const int plane = (qp.bstride ? B : 1) * KVH;
+    const float* sp = qp.scales + (size_t)b * qp.bstride + kvh;
+    qscale *= sp[2 * plane];  // k dequant rides on the q rows
+    vdq = sp[3 * plane];
+    float vt[8];
+    load8<T>(vnew + gl * 8, vt);
+    ktq = quant8(kt, sp[0], qp.round_type, qp.qmax, qp.qmin);
+    vtq = quant8(vt, sp[plane], qp.round_type, qp.qmax, qp.qmin);
+    if (t < hi && wave == 0 && grp == 0) {  // append: one 8-byte store per lane and row
+      *reinterpret_cast<uint2*>(kc + (size_t)t * D + gl * 8) = ktq;
+      *reinterpret_cast<uint2*>(vc + (size_t)t * D + gl * 8) = vtq;
+    }
+  } else if (t < hi && wave == 0 && grp == 0) {  // append the new token (hi > lo here, so t_ok and t >= lo)
     float v[8];
     store8<T>(kc + (size_t)t * D + gl * 8, kt);
     load8<T>(vnew + gl * 8, v);
@@ -176,7 +252,7 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
 #pragma unroll
   for (int r = 0; r < R; ++r) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) q[r][i] *= scale;
+    for (int i = 0; i < 8; ++i) q[r][i] *= qscale;
   }
 
   float m[R], l[R], acc[R][8];
@@ -189,46 +265,119 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
   }
 
   const float* mrow = mask ? mask + (size_t)b * mask_len : nullptr;
-  constexpr int STEP = kWaves * KPW * 2;
-  for (int base = lo; base < hi; base += STEP) {
-    float kx[2][8], vx[2][8], add[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int key = base + (u * kWaves + wave) * KPW + grp;
-      const int kk = key < hi ? key : lo;
-      const T* kp = (kk == t) ? knew : kc + (size_t)kk * D;
-      const T* vp = (kk == t) ? vnew : vc + (size_t)kk * D;
-      load8<T>(kp + gl * 8, kx[u]);
-      load8<T>(vp + gl * 8, vx[u]);
-      if constexpr (EXT) {  // the token's own key: the (rotated, rounded) registers, not the raw row
-        if (kk == t) {
-#pragma unroll
-          for (int i = 0; i < 8; ++i) kx[u][i] = kt[i];
-        }
-      }
-      // a key past the range scores -inf: its weight is exactly 0
-      add[u] = key < hi ? (mrow ? mrow[key] : 0.f) : -INFINITY;
-    }
+  if constexpr (Q8) {
+    // s = q'.(u - 128) = q'.u - qoff, the offset term reduced over the lane group once
+    float qoff[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-      f2 d0 = {0.f, 0.f}, d1 = {0.f, 0.f};  // packed fp32 FMAs: even and odd dims apart
+      float sum = 0.f;
 #pragma unroll
-      for (int i = 0; i < 8; i += 2) {
-        const f2 qq = {q[r][i], q[r][i + 1]};
-        d0 += qq * f2{kx[0][i], kx[0][i + 1]};
-        d1 += qq * f2{kx[1][i], kx[1][i + 1]};
+      for (int i = 0; i < 8; ++i) sum += q[r][i];
+      qoff[r] = 128.f * group_sum<G>(sum);
+    }
+    // keys per lane group per iteration: 4 keep 64 B in flight per lane, as for bf16; the 8
+    // states of R = 8 leave registers for 2 (with 4 it drops to one wave per SIMD and spills)
+    constexpr int U = R >= 8 ? 2 : 4;
+    constexpr int STEP = kWaves * KPW * U;
+    for (int base = lo; base < hi; base += STEP) {
+      uint2 kr[U], vr[U];
+      float add[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int key = base + (u * kWaves + wave) * KPW + grp;
+        const int kk = key < hi ? key : lo;
+        kr[u] = *reinterpret_cast<const uint2*>(kc + (size_t)kk * D + gl * 8);
+        vr[u] = *reinterpret_cast<const uint2*>(vc + (size_t)kk * D + gl * 8);
+        if (kk == t) {  // the token's own row: the quantised registers, not what the slot held
+          kr[u] = ktq;
+          vr[u] = vtq;
+        }
+        add[u] = key < hi ? (mrow ? mrow[key] : 0.f) : -INFINITY;
       }
-      float s0 = d0.x + d0.y, s1 = d1.x + d1.y;
-      s0 = group_sum<G>(s0) + add[0];
-      s1 = group_sum<G>(s1) + add[1];
-      const float mn = fmaxf(m[r], fmaxf(s0, s1));
-      const float ms = (mn == -INFINITY) ? 0.f : mn;  // fully masked so far: every weight below is 0
-      const float c = __expf(m[r] - ms);
-      const float p0 = __expf(s0 - ms), p1 = __expf(s1 - ms);
-      l[r] = l[r] * c + p0 + p1;
+      float pw[R][U], cr[R];
+      {
+        float kf[U][8];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) acc[r][i] = acc[r][i] * c + p0 * vx[0][i] + p1 * vx[1][i];
-      m[r] = mn;
+        for (int u = 0; u < U; ++u) unpack8(kr[u], kf[u]);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          float mn = m[r];
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            f2 d = {0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < 8; i += 2) d += f2{q[r][i], q[r][i + 1]} * f2{kf[u][i], kf[u][i + 1]};
+            pw[r][u] = group_sum<G>(d.x + d.y) - qoff[r] + add[u];
+            mn = fmaxf(mn, pw[r][u]);
+          }
+          const float ms = (mn == -INFINITY) ? 0.f : mn;  // fully masked so far: every weight below is 0
+          cr[r] = __expf(m[r] - ms);
+          float ps = 0.f;
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            pw[r][u] = __expf(pw[r][u] - ms);
+            ps += pw[r][u];
+          }
+          l[r] = l[r] * cr[r] + ps;
+          m[r] = mn;
+        }
+      }
+      float vf[U][8];
+#pragma unroll
+      for (int u = 0; u < U; ++u) unpack8(vr[u], vf[u]);
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          float a = acc[r][i] * cr[r];
+#pragma unroll
+          for (int u = 0; u < U; ++u) a += pw[r][u] * vf[u][i];
+          acc[r][i] = a;
+        }
+      }
+    }
+  } else {
+    constexpr int STEP = kWaves * KPW * 2;
+    for (int base = lo; base < hi; base += STEP) {
+      float kx[2][8], vx[2][8], add[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int key = base + (u * kWaves + wave) * KPW + grp;
+        const int kk = key < hi ? key : lo;
+        const T* kp = (kk == t) ? knew : kc + (size_t)kk * D;
+        const T* vp = (kk == t) ? vnew : vc + (size_t)kk * D;
+        load8<T>(kp + gl * 8, kx[u]);
+        load8<T>(vp + gl * 8, vx[u]);
+        if constexpr (EXT) {  // the token's own key: the (rotated, rounded) registers, not the raw row
+          if (kk == t) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) kx[u][i] = kt[i];
+          }
+        }
+        // a key past the range scores -inf: its weight is exactly 0
+        add[u] = key < hi ? (mrow ? mrow[key] : 0.f) : -INFINITY;
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        f2 d0 = {0.f, 0.f}, d1 = {0.f, 0.f};  // packed fp32 FMAs: even and odd dims apart
+#pragma unroll
+        for (int i = 0; i < 8; i += 2) {
+          const f2 qq = {q[r][i], q[r][i + 1]};
+          d0 += qq * f2{kx[0][i], kx[0][i + 1]};
+          d1 += qq * f2{kx[1][i], kx[1][i + 1]};
+        }
+        float s0 = d0.x + d0.y, s1 = d1.x + d1.y;
+        s0 = group_sum<G>(s0) + add[0];
+        s1 = group_sum<G>(s1) + add[1];
+        const float mn = fmaxf(m[r], fmaxf(s0, s1));
+        const float ms = (mn == -INFINITY) ? 0.f : mn;  // fully masked so far: every weight below is 0
+        const float c = __expf(m[r] - ms);
+        const float p0 = __expf(s0 - ms), p1 = __expf(s1 - ms);
+        l[r] = l[r] * c + p0 + p1;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[r][i] = acc[r][i] * c + p0 * vx[0][i] + p1 * vx[1][i];
+        m[r] = mn;
+      }
     }
   }
 
@@ -265,6 +414,10 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
     float a2[8];
     load8<float>(&s_acc[w][r][gl * 8], a2);
     merge(fm, fl, fa, s_ml[w][r][0], s_ml[w][r][1], a2);
+  }
+  if constexpr (Q8) {  // the V offset and scale, once: the partial leaves dequantised
+#pragma unroll
+    for (int i = 0; i < 8; ++i) fa[i] = (fa[i] - 128.f * fl) * vdq;
   }
   if (splits == 1) {
     const float inv = fl > 0.f ? 1.f / fl : 0.f;
@@ -312,17 +465,27 @@ struct Args {
   const float* rot;
   int rot_dims;
   hipStream_t s;
+  const float* scales;  // 8-bit cache: [4, Bs, KVH], else null
+  int scale_bstride, round_type;
+  float qmax, qmin;
 };
 
-template <typename T, int D, int R, bool EXT>
+template <bool Q8> QParams<Q8> qparams(const Args& a);
+template <> QParams<false> qparams<false>(const Args&) { return {}; }
+template <> QParams<true> qparams<true>(const Args& a) {
+  return {a.scales, a.scale_bstride, a.round_type, a.qmax, a.qmin};
+}
+
+template <typename T, int D, int R, bool EXT, bool Q8 = false>
 int launch(const Args& a) {
   const int keys = a.t_dev ? a.L : a.t + 1;  // device position: splits cover the whole cache
   const int per = (keys + a.splits - 1) / a.splits;
   float* ws_ml = a.ws;
   float* ws_acc = a.ws + (((size_t)a.B * a.H * a.splits * 2 + 3) / 4) * 4;  // 16-B aligned
-  hipLaunchKernelGGL((mmha_split_k<T, D, R, EXT>), dim3(a.splits, a.KVH, a.B), dim3(kWaves * 64), 0, a.s,
-                     (const T*)a.qkv, (T*)a.cache, a.mask, ws_ml, ws_acc, (T*)a.out, a.B, a.KVH, a.L, a.t, a.t_dev,
-                     per, a.mask_len, a.scale, a.seq_lens, a.rot, a.rot_dims);
+  hipLaunchKernelGGL((mmha_split_k<T, D, R, EXT, Q8>), dim3(a.splits, a.KVH, a.B), dim3(kWaves * 64), 0, a.s,
+                     (const T*)a.qkv, (std::conditional_t<Q8, uint8_t, T>*)a.cache, a.mask, ws_ml, ws_acc, (T*)a.out,
+                     a.B, a.KVH, a.L, a.t, a.t_dev, per, a.mask_len, a.scale, a.seq_lens, a.rot, a.rot_dims,
+                     qparams<Q8>(a));
   if (a.splits > 1)
     hipLaunchKernelGGL((mmha_combine_k<T, D>), dim3(a.H, a.B), dim3(D), 0, a.s, ws_ml, ws_acc, (T*)a.out, a.splits);
   return 0;
@@ -330,6 +493,15 @@ int launch(const Args& a) {
 
 template <typename T, int D>
 int launch_r(const Args& a) {
+  if (a.scales) {  // 8-bit cache: EXT instantiations only
+    switch (a.H / a.KVH) {
+      case 1: return launch<T, D, 1, true, true>(a);
+      case 2: return launch<T, D, 2, true, true>(a);
+      case 4: return launch<T, D, 4, true, true>(a);
+      case 8: return launch<T, D, 8, true, true>(a);
+      default: return -1;
+    }
+  }
   switch (a.H / a.KVH) {
     case 1: return (a.seq_lens || a.rot) ? launch<T, D, 1, true>(a) : launch<T, D, 1, false>(a);
     case 2: return launch<T, D, 2, true>(a);
@@ -371,14 +543,27 @@ int pra_mmha_splits(int B, int H, int t) {
 // B*KVH*splits); ws: fp32 workspace of B*H*splits*(2 + D) + 4 floats (unused when splits == 1).
 // seq_lens (device int32 [B]) and rot (device fp32 [2, B, D], rot_dims chunks) are optional.
 // t / t_dev stay the batch-wide bound that the splits were sized for.
+// cache_dt is dt for a float cache (scales null) or kCacheU8 for the 8-bit one: then scales is
+// the packed device fp32 [4, Bs, KVH] (k quant, v quant, k dequant, v dequant) with
+// scale_batch_stride 0 (Bs = 1) or KVH (Bs = B), round_type 1 (half away from zero) or 0 (half
+// to even), and -128 <= qmin < qmax <= 127 the level bounds. Returns non-zero for a
+// (dtype, cache dtype, head dim, ratio) without an instantiation.
 int pra_mmha_decode(const void* qkv, void* cache, const float* mask, float* ws, void* out, int B, int H, int KVH,
                     int L, int D, int t, const int* t_dev, int splits, int mask_len, float scale, int dt,
-                    const int* seq_lens, const float* rot, int rot_dims, hipStream_t s) {
+                    const int* seq_lens, const float* rot, int rot_dims, hipStream_t s, int cache_dt,
+                    const float* scales, int scale_batch_stride, int round_type, float qmax, float qmin) {
   if (splits < 1 || B < 1 || B > 65535 || KVH < 1 || KVH > 65535 || H < KVH || H % KVH != 0 || L < 1) return -1;
   if (!t_dev && (t < 0 || t >= L || (mask && mask_len < t + 1))) return -1;
   if (rot && (rot_dims < 1 || D % (16 * rot_dims) != 0)) return -1;  // a half chunk is whole 8-dim lanes
+  if (cache_dt == kCacheU8) {  // a row piece is one aligned 8-byte access
+    if (!scales || (scale_batch_stride != 0 && scale_batch_stride != KVH) || (round_type != 0 && round_type != 1) ||
+        !(qmin >= -128.f && qmin < qmax && qmax <= 127.f) || ((uintptr_t)cache & 7) != 0)
+      return -1;
+  } else if (cache_dt != dt || scales) {
+    return -1;
+  }
   const Args a{qkv, cache, mask, ws, out, B, H, KVH, L, t, t_dev, splits, mask_len, scale, seq_lens, rot,
-               rot_dims, s};
+               rot_dims, s, scales, scale_batch_stride, round_type, qmax, qmin};
   if (dt == kBF16) return launch_d<bf16>(D, a);
   if (dt == kF16) return launch_d<f16>(D, a);
   if (dt == kF32) return launch_d<float>(D, a);

@@ -766,6 +766,9 @@ def vocab_parallel_cross_entropy(logits, labels, pg=None, world=1, rank=0, ignor
 # Grouped-query attention (the same kernel template, H/KVH query rows per K/V row): a 3-D qkv
 # [B, H + 2*KVH, D] (query heads, then k heads, then v heads) over a cache [2, B, KVH, L, D];
 # query head h reads K/V head h // (H/KVH). The 4-D form is that row with KVH = H.
+# 8-bit cache (the same kernel template again): a uint8 cache of bytes level + 128 with fp32
+# quant / dequant scales per K/V head, [KVH] or per sequence [B, KVH]; kv_quantize and
+# kv_dequantize are the stored byte and the value read back, in torch on both backends.
 # =============================================================================
 def _rotate_rows(x, cos, sin, dims):
     """Half-split rotation inside each of ``dims`` chunks: x [B, H, D] fp32, cos/sin [B, D]."""
@@ -779,8 +782,142 @@ def _rotate_rows(x, cos, sin, dims):
                       right * c[..., half:] + left * sn[..., half:]], -1).reshape(B, H, D)
 
 
+def _kv_scale(s, x):
+    """A quantisation scale against ``x`` [B, KVH, ...]: a number, [KVH] or [B, KVH] (fp32)."""
+    s = torch.as_tensor(s, dtype=torch.float32).to(x.device)
+    if s.dim() == 0:
+        return s
+    if s.dim() == 1:
+        s = s[None]
+    return s.reshape(tuple(s.shape) + (1,) * (x.dim() - 2))
+
+
+def kv_quantize(x, quant_scale, round_type=1, qmax=127.0, qmin=-127.0):
+    """The bytes an 8-bit KV cache stores for ``x`` [B, KVH, ...]: the level
+    ``clamp(round(x_f32 * quant_scale), qmin, qmax)`` (one fp32 multiply, then the rounding;
+    ``round_type`` 1 rounds half away from zero, 0 half to even) plus 128, as ``uint8``.
+    ``quant_scale`` is a number or an fp32 [KVH] or [B, KVH] tensor."""
+    y = x.float() * _kv_scale(quant_scale, x)
+    if int(round_type) == 0:
+        lvl = torch.round(y)
+    else:                                                         # y - trunc(y) is exact
+        tr = torch.trunc(y)
+        lvl = tr + torch.where((y - tr).abs() >= 0.5, torch.sign(y), torch.zeros_like(y))
+    return (lvl.clamp(float(qmin), float(qmax)) + 128.0).to(torch.uint8)
+
+
+def kv_dequantize(u, dequant_scale, dtype=torch.float32):
+    """What an 8-bit KV cache reads back: ``(u - 128) * dequant_scale`` in fp32, cast to
+    ``dtype``. ``u`` is uint8 [B, KVH, ...]; the scale as for ``kv_quantize``."""
+    return ((u.float() - 128.0) * _kv_scale(dequant_scale, u)).to(dtype)
+
+
+def _packed_scales(tensors, shape):
+    """The [4, Bs, KVH] tensor that the four scales are consecutive rows of, if there is one
+    (the decoder runner keeps its scales packed, so a step packs nothing)."""
+    base = getattr(tensors[0], '_base', None)
+    if base is None or tuple(base.shape) != (4,) + shape or not base.is_contiguous() or \
+            base.dtype != torch.float32:
+        return None
+    step = base.stride(0) * 4
+    for i, s in enumerate(tensors):
+        if getattr(s, '_base', None) is not base or not s.is_contiguous() or \
+                s.data_ptr() != base.data_ptr() + i * step:
+            return None
+    return base
+
+
+def _kv_quant_args(B, cache, k_quant, v_quant, k_dequant=None, v_dequant=None, round_type=1,
+                   qmax=127.0, qmin=-127.0, device=None):
+    """Validate the 8-bit cache arguments of ``mmha_decode``. None for a float cache, else
+    (scales fp32 [4, Bs, KVH] = k quant, v quant, k dequant, v dequant on ``device``, the batch
+    stride 0 or KVH, round_type, qmax, qmin)."""
+    given = [s for s in (k_quant, v_quant, k_dequant, v_dequant) if s is not None]
+    if cache.dtype != torch.uint8:
+        if given:
+            raise ValueError(f"mmha_decode: cache quantisation scales with a {cache.dtype} cache; "
+                             "they go with a uint8 cache")
+        return None
+    if cache.dim() != 5:
+        raise ValueError(f"mmha_decode: a uint8 cache must be [2, B, KVH, L, D], got {tuple(cache.shape)}")
+    if k_quant is None or v_quant is None:
+        raise ValueError("mmha_decode: a uint8 cache needs cache_k_quant_scales and "
+                         "cache_v_quant_scales")
+    KVH = cache.shape[2]
+    for s in given:
+        if not isinstance(s, torch.Tensor) or s.dtype != torch.float32 or \
+                tuple(s.shape) not in ((KVH,), (B, KVH)) or s.shape != k_quant.shape:
+            raise ValueError(f"mmha_decode: cache quantisation scales must be fp32 tensors, all "
+                             f"[{KVH}] or all [{B}, {KVH}]; got "
+                             f"{getattr(s, 'dtype', type(s).__name__)} {tuple(getattr(s, 'shape', ()))}")
+        if not s.is_cuda and not bool((torch.isfinite(s) & (s > 0)).all()):
+            raise ValueError("mmha_decode: cache quantisation scales must be finite and positive")
+    if int(round_type) not in (0, 1):
+        raise ValueError(f"mmha_decode: quant_round_type must be 0 (half to even) or 1 (half away "
+                         f"from zero), got {round_type}")
+    qmax, qmin = float(qmax), float(qmin)
+    if not (-128.0 <= qmin < qmax <= 127.0):
+        raise ValueError(f"mmha_decode: need -128 <= quant_min_bound < quant_max_bound <= 127, got "
+                         f"{qmin} and {qmax}")
+    shape = (1, KVH) if k_quant.dim() == 1 else (B, KVH)
+    four = [k_quant, v_quant, k_dequant, v_dequant]
+    packed = _packed_scales(four, shape) if len(given) == 4 else None
+    if packed is None:
+        four[2] = 1.0 / k_quant if k_dequant is None else k_dequant
+        four[3] = 1.0 / v_quant if v_dequant is None else v_dequant
+        packed = torch.stack([s.reshape(shape) for s in four])
+    if device is not None:
+        packed = packed.to(device)
+    return packed.contiguous(), (0 if shape[0] == 1 else KVH), int(round_type), qmax, qmin
+
+
+def _mmha_ref_q8(qkv, cache, t, mask, seq_lens, rotary, rotary_dims, quant):
+    """The contract of the 8-bit cache in torch, for any ratio and head dim: the oracle of the
+    Q8 HIP kernels. The new k (rotated in fp32, not rounded to the model dtype) and v are
+    quantised from fp32, written at t_b, and attended to as those levels like any cached row."""
+    R._STATS[('mmha_decode_q8', 'ref')] += 1
+    scales, _, round_type, qmax, qmin = quant
+    B, D, KVH, L = qkv.shape[0], qkv.shape[-1], cache.shape[2], cache.shape[3]
+    bound = L - 1
+    if isinstance(t, torch.Tensor):
+        t = int(t.reshape(-1)[0])
+    else:
+        bound = t
+    if qkv.dim() == 3:
+        R._STATS[('mmha_decode_gqa', 'ref')] += 1
+    row = qkv.reshape(B, -1, D).float()
+    H = row.shape[1] - 2 * KVH
+    q, k, v = row[:, :H], row[:, H:H + KVH], row[:, H + KVH:]
+    if rotary is not None:
+        R._STATS[('mmha_decode_rotary', 'ref')] += 1
+        cos, sin = rotary.reshape(2, B, D).float().to(qkv.device)
+        q, k = _rotate_rows(q, cos, sin, rotary_dims), _rotate_rows(k, cos, sin, rotary_dims)
+    kq, vq, kdq, vdq = scales.to(qkv.device).expand(4, B, KVH)
+    ku = kv_quantize(k, kq, round_type, qmax, qmin)               # [B, KVH, D] bytes
+    vu = kv_quantize(v, vq, round_type, qmax, qmin)
+    lens = [t] * B if seq_lens is None else [int(x) for x in seq_lens.reshape(-1).tolist()]
+    mrows = None if mask is None else mask.reshape(B, -1).float()
+    out = torch.zeros(B, H, D, device=qkv.device, dtype=torch.float32)
+    for b, tb in enumerate(lens):
+        if not (0 <= tb < L and tb <= bound) or (mrows is not None and mrows.shape[1] < tb + 1):
+            continue                                              # guarded: zeros out, no write
+        cache[0, b, :, tb] = ku[b]
+        cache[1, b, :, tb] = vu[b]
+        K_ = kv_dequantize(cache[0, b:b + 1, :, :tb + 1], kdq[b:b + 1])[0]
+        V_ = kv_dequantize(cache[1, b:b + 1, :, :tb + 1], vdq[b:b + 1])[0]
+        if H > KVH:
+            K_, V_ = K_.repeat_interleave(H // KVH, 0), V_.repeat_interleave(H // KVH, 0)
+        s = torch.einsum('hd,hld->hl', q[b], K_) / math.sqrt(D)
+        if mrows is not None:
+            s = s + mrows[b, None, :tb + 1]
+        out[b] = torch.einsum('hl,hld->hd', torch.softmax(s, -1), V_)
+    return out.to(qkv.dtype)
+
+
 @R.register_kernel('mmha_decode', 'ref')
-def _mmha_ref(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0):
+def _mmha_ref(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0, quant=None):
+    if quant is not None:
+        return _mmha_ref_q8(qkv, cache, t, mask, seq_lens, rotary, rotary_dims, quant)
     L = cache.shape[3]
     bound = L - 1  # a tensor position is a device position: no batch-wide bound below L
     if isinstance(t, torch.Tensor):
@@ -830,7 +967,7 @@ def _mmha_ref(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0):
 
 
 @R.register_kernel('mmha_decode', 'hip', dtypes=_FLOATS)
-def _mmha_hip(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0):
+def _mmha_hip(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0, quant=None):
     if qkv.dim() == 3:              # [B, H + 2*KVH, D]; the 4-D form is the same memory with KVH = H
         B, D, KVH = qkv.shape[0], qkv.shape[2], cache.shape[2]
         H = qkv.shape[1] - 2 * KVH
@@ -846,7 +983,10 @@ def _mmha_hip(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0):
         if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
             raise ValueError("mmha_decode: a tensor time_step must be a CUDA int32 tensor")
         t_dev, t = t, 0
-    if not (qkv.is_contiguous() and cache.is_contiguous() and cache.dtype == qkv.dtype and
+    # a uint8 cache comes with its scales; its row pieces are aligned 8-byte accesses
+    cache_ok = cache.dtype == qkv.dtype if quant is None else \
+        (cache.dtype == torch.uint8 and cache.is_cuda and cache.data_ptr() % 8 == 0)
+    if not (qkv.is_contiguous() and cache.is_contiguous() and cache_ok and
             tuple(cache.shape) == (2, B, KVH, L, D) and D in (64, 128, 256) and
             (t_dev is not None or 0 <= t < L)):
         raise ValueError(f"mmha_decode: qkv {tuple(qkv.shape)} / cache {tuple(cache.shape)} / "
@@ -875,6 +1015,21 @@ def _mmha_hip(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0):
             raise ValueError(f"mmha_decode: mask covers {mlen} positions, need {t + 1}")
     if H > KVH:
         R._STATS[('mmha_decode_gqa', 'hip')] += 1
+    if quant is not None:
+        scales, bstride, round_type, qmax, qmin = quant
+        if not (scales.is_cuda and scales.dtype == torch.float32 and scales.is_contiguous() and
+                tuple(scales.shape) == (4, B if bstride else 1, KVH) and bstride in (0, KVH)):
+            raise ValueError(f"mmha_decode: the packed cache scales must be a contiguous CUDA fp32 "
+                             f"[4, 1 or {B}, {KVH}] tensor")
+        R._STATS[('mmha_decode_q8', 'hip')] += 1
+        _native.lib().mmha_decode_q8(_ptr(qkv), _ptr(cache), _ptr(mask) if mask is not None else 0,
+                                     _ptr(ws), _ptr(out), B, H, KVH, L, D, int(t),
+                                     _ptr(t_dev) if t_dev is not None else 0, splits, mlen,
+                                     1.0 / math.sqrt(D), _dt(qkv), _stream(),
+                                     _ptr(seq_lens) if seq_lens is not None else 0,
+                                     _ptr(rotary) if rotary is not None else 0, int(rotary_dims),
+                                     _ptr(scales), bstride, round_type, qmax, qmin)
+        return out
     _native.lib().mmha_decode(_ptr(qkv), _ptr(cache), _ptr(mask) if mask is not None else 0,
                               _ptr(ws), _ptr(out), B, H, KVH, L, D, int(t),
                               _ptr(t_dev) if t_dev is not None else 0, splits, mlen,
@@ -894,7 +1049,10 @@ def rotary_in_kernel(head_dim, rotary_dims):
             head_dim % (16 * rotary_dims) == 0)
 
 
-def mmha_decode(qkv, cache, time_step, mask=None, seq_lens=None, rotary=None, rotary_dims=0):
+def mmha_decode(qkv, cache, time_step, mask=None, seq_lens=None, rotary=None, rotary_dims=0,
+                cache_k_quant_scales=None, cache_v_quant_scales=None, cache_k_dequant_scales=None,
+                cache_v_dequant_scales=None, quant_round_type=1, quant_max_bound=127.0,
+                quant_min_bound=-127.0):
     """One decode step of multi-head attention; returns [B, H, D] and appends K/V to
     ``cache`` at ``time_step`` in place. ``time_step`` may be a CUDA int32 tensor: the kernel
     reads it on the device (no host sync), so the step can live in a captured HIP graph.
@@ -910,9 +1068,24 @@ def mmha_decode(qkv, cache, time_step, mask=None, seq_lens=None, rotary=None, ro
     Grouped-query attention: a 3-D ``qkv`` [B, H + 2*KVH, D] (the H query heads, then the KVH
     k heads, then the KVH v heads) with ``cache`` [2, B, KVH, L, D]; query head ``h`` reads
     K/V head ``h // (H // KVH)``. ``KVH == H`` is the 4-D form; on the GPU the ratio H / KVH
-    must be one of ``GQA_RATIOS``."""
+    must be one of ``GQA_RATIOS``.
+
+    8-bit cache: a ``torch.uint8`` ``cache`` holds, for a value x, the byte ``level + 128`` with
+    ``level = clamp(round(x_f32 * quant_scale), quant_min_bound, quant_max_bound)`` and reads it
+    back as ``(byte - 128) * dequant_scale`` (``kv_quantize`` / ``kv_dequantize``).
+    ``cache_k_quant_scales`` and ``cache_v_quant_scales`` are required with it and refused
+    without it: fp32 tensors, [KVH] per K/V head or [B, KVH] per sequence and head; the dequant
+    scales default to ``1 / quant_scale``. Host scales must be finite and positive; device
+    scales are not synced. ``quant_round_type`` 1 rounds half away from zero, 0 half to even.
+    The new token's k (rotated first, not rounded to the model dtype) and v are quantised from
+    fp32, written at ``t_b`` and attended to as those levels, so a later step that reads the
+    row back agrees with this one. Everything else behaves as for a float cache."""
     if not isinstance(time_step, torch.Tensor):
         time_step = int(time_step)
+    quant = _kv_quant_args(qkv.shape[0], cache, cache_k_quant_scales, cache_v_quant_scales,
+                           cache_k_dequant_scales, cache_v_dequant_scales, quant_round_type,
+                           quant_max_bound, quant_min_bound, qkv.device)
+    qkw = {} if quant is None else {'quant': quant}
     if qkv.dim() == 3:
         if cache.dim() != 5 or cache.shape[1] != qkv.shape[0] or cache.shape[4] != qkv.shape[2]:
             raise ValueError(f"mmha_decode: cache {tuple(cache.shape)} does not fit qkv "
@@ -926,7 +1099,7 @@ def mmha_decode(qkv, cache, time_step, mask=None, seq_lens=None, rotary=None, ro
         if H == KVH:
             qkv = qkv.reshape(qkv.shape[0], 3, H, qkv.shape[2])
     if seq_lens is None and rotary is None:
-        return R.dispatch('mmha_decode', qkv, qkv.contiguous(), cache, time_step, mask)
+        return R.dispatch('mmha_decode', qkv, qkv.contiguous(), cache, time_step, mask, **qkw)
     B, D = qkv.shape[0], qkv.shape[-1]
     if seq_lens is not None:
         on_host = not (isinstance(seq_lens, torch.Tensor) and seq_lens.is_cuda)
@@ -946,7 +1119,7 @@ def mmha_decode(qkv, cache, time_step, mask=None, seq_lens=None, rotary=None, ro
             raise ValueError("mmha_decode: rotary needs rotary_dims >= 1")
         rotary = rotary.reshape(2, B, D).to(device=qkv.device, dtype=torch.float32).contiguous()
     return R.dispatch('mmha_decode', qkv, qkv.contiguous(), cache, time_step, mask,
-                      seq_lens=seq_lens, rotary=rotary, rotary_dims=int(rotary_dims))
+                      seq_lens=seq_lens, rotary=rotary, rotary_dims=int(rotary_dims), **qkw)
 
 
 # =============================================================================

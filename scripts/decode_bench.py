@@ -1,6 +1,8 @@
 """Decode-attention bandwidth: the HIP split-K kernel (K.mmha_decode) vs torch SDPA over
 the same KV cache, a ragged batch (per-sequence seq_lens) next to its padded-and-masked twin,
-grouped-query attention next to the expanded multi-head cache and the byte floor, and end-to-end FusedMultiTransformer decode steps/s.
+grouped-query attention next to the expanded multi-head cache and the byte floor, end-to-end
+FusedMultiTransformer decode steps/s, and the 8-bit KV cache next to the bf16 one (kernel rows
+and the graph decoder).
 
 usage: python scripts/decode_bench.py [--quick]"""
 import argparse
@@ -20,6 +22,27 @@ def bench(fn, iters=50, warmup=5):
         fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / iters
+
+
+def bench_graph(fn, calls=20, reps=10):
+    """Per-call time of ``fn`` replayed from one captured HIP graph of ``calls`` calls: the
+    kernels back to back, without the host's launch path between them."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()
+    torch.cuda.current_stream().wait_stream(side)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(calls):
+            fn()
+    g.replay()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        g.replay()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / (reps * calls)
 
 
 def main():
@@ -122,7 +145,51 @@ def main():
     print(json.dumps(dict(model=f'{L}x{E} FusedMultiTransformerDecoder (HIP graph)', batch=B,
                           ctx=ctx, ms_per_token_step=round(dg * 1e3, 3),
                           tokens_per_s=round(B / dg, 1))), flush=True)
+    # the graph decoder again, its caches 8-bit
+    mib16 = sum(c[:, 0].numel() * c.element_size() for c in dec.caches) / 2 ** 20
+    dec8 = FusedMultiTransformerDecoder(m, B, ctx + 256, kv_cache_dtype='int8')
+    dec8.t.fill_(ctx)
 
+    def gstep8():
+        dec8.step(xt)
+        dec8.t.fill_(ctx)
+    d8 = bench(gstep8, iters=50, warmup=3)
+    mib8 = sum(c[:, 0].numel() * c.element_size() for c in dec8.caches) / 2 ** 20
+    print(json.dumps(dict(model=f'{L}x{E} FusedMultiTransformerDecoder (HIP graph, int8 KV cache)',
+                          batch=B, ctx=ctx, ms_per_token_step=round(d8 * 1e3, 3),
+                          bf16_cache_ms_per_token_step=round(dg * 1e3, 3),
+                          tokens_per_s=round(B / d8, 1), cache_MiB_per_sequence_bf16=round(mib16, 1),
+                          cache_MiB_per_sequence_int8=round(mib8, 1))), flush=True)
+    # 8-bit KV cache (uint8 + per-head scales) next to the bf16 cache on the same problem: the
+    # plain shapes at batch 1 and 8, then the two grouped-query shapes. TB/s counts the cache
+    # bytes each kernel streams: 1 byte per element for int8, 2 for bf16. The *_graph_us columns
+    # replay the same calls from a captured HIP graph, as the decoder runner does: at these
+    # sizes the eager columns of the smaller rows are the host's launch path, not the kernel.
+    for Bq, H, KVH in ((1, 32, 32), (8, 32, 32), (8, 32, 8), (8, 64, 8)):
+        D, t = 128, 4095
+        row = torch.randn(Bq, H + 2 * KVH, D, device='cuda', dtype=torch.bfloat16)
+        if H == KVH:
+            row = row.reshape(Bq, 3, H, D)
+        cache16 = torch.randn(2, Bq, KVH, t + 1, D, device='cuda', dtype=torch.bfloat16)
+        packed = torch.empty(4, 1, KVH, device='cuda')          # k quant, v quant, k dequant, v dequant
+        packed[:2] = 127.0 / 4.5
+        packed[2:] = 4.5 / 127.0
+        cache8 = torch.stack([K.kv_quantize(cache16[i], packed[i, 0]) for i in range(2)])
+        kw = dict(cache_k_quant_scales=packed[0, 0], cache_v_quant_scales=packed[1, 0],
+                  cache_k_dequant_scales=packed[2, 0], cache_v_dequant_scales=packed[3, 0])
+        bf = bench(lambda: K.mmha_decode(row, cache16, t))
+        q8 = bench(lambda: K.mmha_decode(row, cache8, t, **kw))
+        with torch.no_grad():
+            bfg = bench_graph(lambda: K.mmha_decode(row, cache16, t))
+            q8g = bench_graph(lambda: K.mmha_decode(row, cache8, t, **kw))
+        elems = 2 * Bq * KVH * (t + 1) * D
+        print(json.dumps(dict(B=Bq, H=H, KVH=KVH, D=D, ctx=t + 1, int8_us=round(q8 * 1e6, 1),
+                              bf16_us=round(bf * 1e6, 1), int8_over_bf16=round(q8 / bf, 3),
+                              int8_graph_us=round(q8g * 1e6, 1), bf16_graph_us=round(bfg * 1e6, 1),
+                              int8_graph_TBps=round(elems / q8g / 1e12, 2),
+                              bf16_graph_TBps=round(2 * elems / bfg / 1e12, 2),
+                              int8_over_bf16_graph=round(q8g / bfg, 3))), flush=True)
+        del cache16, cache8
 
 if __name__ == '__main__':
     main()
