@@ -178,17 +178,12 @@ class DistributedFusedLamb(Optimizer):
         norm = sq.sqrt()
         return clip_norm / torch.maximum(norm, torch.full_like(norm, clip_norm))
 
-    def _hip(self, s):
-        if not s.m.is_cuda:
-            return None
-        from ...ops import _native
-        return _native.lib() if _native.available() else _native.require()
-
     def _stage1(self, s, gscale, coef_t, bc1, bc2):
-        L = self._hip(s)
         g = s.grad_shard
-        if L is not None:
+        if s.m.is_cuda:     # a CUDA shard runs the HIP kernels (a missing library is an error)
+            from ...ops import _native
             from ...ops.fused import _dt, _stream
+            L = _native.lib()
             L.lamb_shard_stage1(s.pieces.data_ptr(), s.npieces, g.data_ptr(), _dt(g), s.master.data_ptr(),
                                 s.m.data_ptr(), s.v.data_ptr(), s.r.data_ptr(), s.wd.data_ptr(), s.norms.data_ptr(),
                                 s.P, self._beta1, self._beta2, self._epsilon, bc1, bc2, gscale,
@@ -198,9 +193,10 @@ class DistributedFusedLamb(Optimizer):
                         self._epsilon, bc1, bc2, gscale * (float(coef_t) if coef_t is not None else 1.0))
 
     def _stage2(self, s, lr):
-        L = self._hip(s)
-        if L is not None:
+        if s.m.is_cuda:
+            from ...ops import _native
             from ...ops.fused import _dt, _stream
+            L = _native.lib()
             L.lamb_shard_stage2(s.pieces.data_ptr(), s.npieces, s.master.data_ptr(), s.r.data_ptr(),
                                 s.norms.data_ptr(), s.P, lr, s.pshard.data_ptr(), _dt(s.pshard), _stream())
             # padding between parameters (and past the last one) keeps the old values

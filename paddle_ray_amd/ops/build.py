@@ -142,8 +142,8 @@ def build(force=False, verbose=True):
     bobj = os.path.join(BUILD, 'bindings.o')
     objs.append(bobj)
     bcmd = [HIPCC, '-O2', '-fPIC', '-std=c++17', '-c', bsrc, '-o', bobj,
-            '-I', pybind11.get_include(), '-I', sysconfig.get_paths()['include']]
-    keys['bindings.o'] = _digest([bsrc], bcmd)
+            '-I', CSRC, '-I', pybind11.get_include(), '-I', sysconfig.get_paths()['include']]
+    keys['bindings.o'] = _digest([bsrc] + _header_closure(bsrc), bcmd)
     if force or _needs(bobj, keys['bindings.o'], manifest):
         jobs.append(bcmd)
     with cf.ThreadPoolExecutor(max_workers=min(8, max(1, len(jobs)))) as ex:
@@ -153,13 +153,13 @@ def build(force=False, verbose=True):
     info = {'sources_sha256': sources_hash(), 'arch': ARCH, 'hipcc': _hipcc_version()}
     isrc = os.path.join(BUILD, 'build_info.cpp')
     iobj = os.path.join(BUILD, 'build_info.o')
-    text = ('extern "C" const char* pra_build_info() { return R"PRA(' + json.dumps(info) +
+    text = ('#include "pra_api.h"\nconst char* pra_build_info() { return R"PRA(' + json.dumps(info) +
             ')PRA"; }\n')
     old = open(isrc).read() if os.path.exists(isrc) else None
     if old != text or not os.path.exists(iobj):
         with open(isrc, 'w') as f:
             f.write(text)
-        _run([HIPCC, '-O2', '-fPIC', '-c', isrc, '-o', iobj])
+        _run([HIPCC, '-O2', '-fPIC', '-c', isrc, '-o', iobj, '-I', CSRC])
         jobs.append('build_info')
     objs.append(iobj)
     out = _out_path()

@@ -17,6 +17,7 @@
 //   bn_bwd_apply_k          dx = a*g + c1*x + c0 (+ dz = g)
 // The row-block partials are written once and merged deterministically (no float atomics).
 #include "common.h"
+#include "pra_api.h"
 
 namespace pra {
 

@@ -56,6 +56,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "pra_api.h"
 
 namespace pra {
 namespace {

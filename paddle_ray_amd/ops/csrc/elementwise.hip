@@ -4,6 +4,7 @@
 //   multi-tensor Momentum, sum-of-squares (global-norm clipping), attention
 //   backward preprocess delta = rowsum(dO * O).
 #include "common.h"
+#include "pra_api.h"
 
 namespace pra {
 

@@ -13,6 +13,7 @@
 //           no dense [V, D] temporary or extra add pass exists). Runs own disjoint rows: no
 //           races.
 #include "common.h"
+#include "pra_api.h"
 
 namespace pra {
 

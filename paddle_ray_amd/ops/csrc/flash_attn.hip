@@ -26,6 +26,7 @@
 // fwd / dQ: 8 waves, 32 queries per wave (2 waves per SIMD); dK/dV: 4 waves, 32 keys per
 // wave (one wave per SIMD, 256 + accumulator registers).
 #include "common.h"
+#include "pra_api.h"
 #include <stdlib.h>
 #include <string.h>
 #include <type_traits>

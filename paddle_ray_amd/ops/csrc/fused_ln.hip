@@ -15,6 +15,7 @@
 // Parity: paddle/fluid/operators/fused/fused_dropout_helper.h,
 // fused_layernorm_residual_dropout_bias.h (FusedBiasDropoutResidualLayerNorm).
 #include "common.h"
+#include "pra_api.h"
 #include <stdlib.h>
 
 namespace pra {

@@ -18,6 +18,7 @@
 // each XCD gets a contiguous run of tiles, then grouped 8 M-tiles at a time so neighbouring
 // tiles share A/B panels inside one XCD's L2.
 #include "common.h"
+#include "pra_api.h"
 
 namespace pra {
 namespace {

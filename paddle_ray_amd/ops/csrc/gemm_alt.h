@@ -3,6 +3,7 @@
 // TU per configuration family so the heavy instantiations compile in parallel).
 #pragma once
 #include "gemm_core.h"
+#include "pra_api.h"
 
 namespace pra {
 namespace {

@@ -1,6 +1,7 @@
 // MUBUF-DMA (W4B / W8B) and two-barrier early-refill (W4P / W8P) GEMM configurations
 // (gemm_core.h; dispatcher in gemm_w4.hip).
 #include "gemm_alt.h"
+#include "pra_api.h"
 
 namespace pra {
 namespace {

@@ -1,5 +1,6 @@
 // TS-schedule GEMM configurations (gemm_core.h kstep_t; dispatcher in gemm_w4.hip).
 #include "gemm_alt.h"
+#include "pra_api.h"
 
 namespace pra {
 namespace {

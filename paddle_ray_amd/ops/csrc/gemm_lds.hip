@@ -34,20 +34,7 @@
 // column partial sums written to `colsum` (the bias gradient, reduced by pra_colsum_partials);
 // `beta=1` accumulates into C (dW += xᵀ·dy straight into the flat gradient buffer).
 #include "gemm_core.h"
-
-extern "C" int pra_gemm_alt(int cfg, int layout, const void* A, const void* B, const void* bias, void* C, void* Z,
-                            float* colsum, int M, int N, int K, int lda, int ldb, int ldc, int ldz, int dtype, int epi,
-                            int beta, int splits, float* ws, hipStream_t s);
-
-extern "C" int pra_gemm_pts_w4(int layout, const void* A, const void* B, const void* bias, void* C, void* Z,
-                               float* colsum, int M, int N, int K, int lda, int ldb, int ldc, int ldz, int dtype,
-                               int epi, int beta, hipStream_t s);
-extern "C" int pra_gemm_pts_w4b(int layout, const void* A, const void* B, const void* bias, void* C, void* Z,
-                                float* colsum, int M, int N, int K, int lda, int ldb, int ldc, int ldz, int dtype,
-                                int epi, int beta, hipStream_t s);
-extern "C" int pra_gemm_pts_w8(int layout, const void* A, const void* B, const void* bias, void* C, void* Z,
-                               float* colsum, int M, int N, int K, int lda, int ldb, int ldc, int ldz, int dtype,
-                               int epi, int beta, hipStream_t s);
+#include "pra_api.h"
 
 namespace pra {
 namespace {
@@ -304,8 +291,8 @@ extern "C" int pra_conv_lds_stat_rows(int M, int Cout) { return (M + pra::conv_t
 // beta (bnx only): Y holds a pending gradient that is added to the product before the mask.
 extern "C" int pra_conv_lds(const void* x, const void* W, const void* bias, void* Y, int Nimg, int H, int Wd,
                             int C, int Cout, int KH, int KW, int S, int P, int relu, int dtype, int splits, float* ws,
-                            float* part, const float* kshift, int pp, hipStream_t s, const void* bnx = nullptr,
-                            const uint8_t* bnmask = nullptr, int beta = 0) {
+                            float* part, const float* kshift, int pp, hipStream_t s, const void* bnx,
+                            const uint8_t* bnmask, int beta) {
   if (pp <= 0) pp = C;
   if (bnx && (!bnmask || !part || !kshift || relu || bias || splits > 1)) return -1;
   if (C % 64 || Cout % 8 || KH <= 0 || KW <= 0 || S <= 0 || P < 0 || H <= 0 || Wd <= 0) return -1;
@@ -396,7 +383,6 @@ extern "C" int pra_conv_wgrad_lds(const void* dy, const void* x, void* dW, int N
 }
 
 // Split-K factor for an implicit-GEMM conv (1 for the narrow-tile configs, Cout <= 128)
-extern "C" int pra_gemm_lds_splits(int M, int N, int K);
 extern "C" int pra_conv_lds_splits(int M, int Cout, int K) { return Cout <= 128 ? 1 : pra_gemm_lds_splits(M, Cout, K); }
 
 // Split-K factor for a problem: 1 unless the tile grid leaves CUs idle (fewer than ~224 tiles

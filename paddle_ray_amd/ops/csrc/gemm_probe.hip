@@ -3,6 +3,7 @@
 // Timing tools only (scripts/gemm_stamps.py); no framework op calls it.
 #define PRA_GEMM_STAMPS 1
 #include "gemm_core.h"
+#include "pra_api.h"
 
 namespace pra {
 namespace {

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "gemm_pts.h"
+#include "pra_api.h"
 
 namespace pra {
 namespace {

@@ -9,6 +9,7 @@
 // schedule (A/B against the burst schedule of gemm_lds.hip's W8), and holds the configuration
 // dispatcher; the other families live in gemm_alt_bp.hip / gemm_alt_t.hip.
 #include "gemm_alt.h"
+#include "pra_api.h"
 
 namespace pra {
 namespace {
@@ -18,16 +19,6 @@ using W8I = WCfg<2, 4, 256, 256, true>;
 
 PRA_GEMM_ALT_ENTRY(pra_gemm_w4, pra::W4)
 PRA_GEMM_ALT_ENTRY(pra_gemm_w8i, pra::W8I)
-
-#define PRA_ALT_DECL(NAME)                                                                                  \
-  extern "C" int NAME(int, const void*, const void*, const void*, void*, void*, float*, int, int, int, int,   \
-                      int, int, int, int, int, int, int, float*, hipStream_t);
-PRA_ALT_DECL(pra_gemm_w4b)
-PRA_ALT_DECL(pra_gemm_w8b)
-PRA_ALT_DECL(pra_gemm_w4p)
-PRA_ALT_DECL(pra_gemm_w8p)
-PRA_ALT_DECL(pra_gemm_w4t)
-PRA_ALT_DECL(pra_gemm_w8t)
 
 // cfg: 0 = W4, 1 = W8I, 2 = W4B, 3 = W8B, 4 = W4P, 5 = W8P, 6 = W4T, 7 = W8T
 extern "C" int pra_gemm_alt(int cfg, int layout, const void* A, const void* B, const void* bias, void* C, void* Z,

@@ -12,6 +12,7 @@
 //            updated master goes to the shard of the parameter buffer in the parameter's dtype
 //            (what the all-gather then distributes).
 #include "common.h"
+#include "pra_api.h"
 
 namespace pra {
 namespace {

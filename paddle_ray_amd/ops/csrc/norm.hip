@@ -4,6 +4,7 @@
 // Backward: grid-stride over rows with per-workgroup fp32 dW/dB partials kept in
 // registers, reduced by `colsum` (deterministic, no float atomics).
 #include "common.h"
+#include "pra_api.h"
 
 namespace pra {
 

@@ -7,6 +7,7 @@
 //                    windows that contain it whose stored tap is this pixel. No atomics, no
 //                    zero-fill pass, dx written once with 16-B stores.
 #include "common.h"
+#include "pra_api.h"
 
 namespace pra {
 

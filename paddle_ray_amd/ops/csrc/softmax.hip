@@ -3,6 +3,7 @@
 // 16-byte loads; CE backward writes dlogits = (softmax - onehot) * dloss in one
 // pass (the [tokens, vocab] probability matrix is never materialised).
 #include "common.h"
+#include "pra_api.h"
 
 namespace pra {
 

@@ -161,27 +161,29 @@ def _ln_bwd_hip(dy, x2, w, mean, rstd, need_dw, need_db, pdt=None):
     pdt = w.dtype if w is not None else (pdt or x2.dtype)
     dtw = _wdt('layer_norm_grad', x2, w)
     dy = dy.contiguous()
-    if _adl_ok(cols):
+    adl = _adl_ok(cols)
+    if adl:
         nblk = _adl_nblk(rows)
         part = torch.empty((2, nblk, cols), device=x2.device, dtype=torch.float32)
         L.adl_bwd(_ptr(dy), 0, _ptr(x2), _ptr(w), _ptr(mean), _ptr(rstd), _ptr(dx), 0,
                   _ptr(part[0]) if (need_dw and w is not None) else 0,
                   _ptr(part[1]) if need_db else 0, 0, rows, cols, nblk, 0.0, 0, 0, 0, _dt(x2), dtw,
                   _stream())
-        red = L.colsum16
     else:
         nblk = _colsum_nblk(rows)
         part = torch.empty((2, nblk, cols), device=x2.device, dtype=torch.float32)
         L.layernorm_bwd(_ptr(dy), _ptr(x2), _ptr(w), _ptr(mean), _ptr(rstd), _ptr(dx),
                         _ptr(part[0]), _ptr(part[1]), rows, cols, nblk, _dt(x2), dtw, _stream())
-        red = L.colsum
-    dw = db = None
-    if need_dw and w is not None:
-        dw = torch.empty(cols, device=x2.device, dtype=pdt)
-        red(_ptr(part[0]), _ptr(dw), nblk, cols, _DT[pdt], _stream())
-    if need_db:
-        db = torch.empty(cols, device=x2.device, dtype=pdt)
-        red(_ptr(part[1]), _ptr(db), nblk, cols, _DT[pdt], _stream())
+
+    def red(src):
+        out = torch.empty(cols, device=x2.device, dtype=pdt)
+        if adl:
+            L.colsum16(_ptr(src), _ptr(out), nblk, cols, _DT[pdt], _stream())
+        else:
+            L.colsum(_ptr(src), _ptr(out), nblk, cols, _DT[pdt], _stream())
+        return out
+    dw = red(part[0]) if need_dw and w is not None else None
+    db = red(part[1]) if need_db else None
     return dx, dw, db
 
 
@@ -379,7 +381,10 @@ def _adl_bwd_hip(dy, dr_out, r, w, mean, rstd, p, seed, need_dw, need_db, need_d
                        [a for _, _, a in jobs], nblk, cols, _DT[jobs[0][1].dtype], _stream())
     else:
         for i, o, a in jobs:
-            (L.colsum16_acc if a else L.colsum16)(_ptr(part[i]), _ptr(o), nblk, cols, _DT[o.dtype], _stream())
+            if a:
+                L.colsum16_acc(_ptr(part[i]), _ptr(o), nblk, cols, _DT[o.dtype], _stream())
+            else:
+                L.colsum16(_ptr(part[i]), _ptr(o), nblk, cols, _DT[o.dtype], _stream())
     return (dri, dh) + tuple(outs)
 
 
@@ -1022,21 +1027,21 @@ def _mmha_hip(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0, qu
             raise ValueError(f"mmha_decode: the packed cache scales must be a contiguous CUDA fp32 "
                              f"[4, 1 or {B}, {KVH}] tensor")
         R._STATS[('mmha_decode_q8', 'hip')] += 1
-        _native.lib().mmha_decode_q8(_ptr(qkv), _ptr(cache), _ptr(mask) if mask is not None else 0,
-                                     _ptr(ws), _ptr(out), B, H, KVH, L, D, int(t),
-                                     _ptr(t_dev) if t_dev is not None else 0, splits, mlen,
-                                     1.0 / math.sqrt(D), _dt(qkv), _stream(),
-                                     _ptr(seq_lens) if seq_lens is not None else 0,
-                                     _ptr(rotary) if rotary is not None else 0, int(rotary_dims),
-                                     _ptr(scales), bstride, round_type, qmax, qmin)
-        return out
+        cache_dt, scales_ptr = _CACHE_U8, _ptr(scales)
+    else:
+        # a float cache: the model dtype's code, no scales (the quantisation arguments unused)
+        cache_dt, scales_ptr, bstride, round_type, qmax, qmin = _dt(qkv), 0, 0, 1, 127.0, -127.0
     _native.lib().mmha_decode(_ptr(qkv), _ptr(cache), _ptr(mask) if mask is not None else 0,
                               _ptr(ws), _ptr(out), B, H, KVH, L, D, int(t),
                               _ptr(t_dev) if t_dev is not None else 0, splits, mlen,
-                              1.0 / math.sqrt(D), _dt(qkv), _stream(),
+                              1.0 / math.sqrt(D), _dt(qkv),
                               _ptr(seq_lens) if seq_lens is not None else 0,
-                              _ptr(rotary) if rotary is not None else 0, int(rotary_dims))
+                              _ptr(rotary) if rotary is not None else 0, int(rotary_dims), _stream(),
+                              cache_dt, scales_ptr, bstride, round_type, qmax, qmin)
     return out
+
+
+_CACHE_U8 = 3            # cache dtype code of the uint8 KV cache (decode_attn.hip kCacheU8)
 
 
 GQA_RATIOS = (2, 4, 8)   # query heads per K/V head the HIP grouped-query kernel is built for
@@ -1304,7 +1309,7 @@ def _fa_bwd_hip(do, q, k, v, o, lse, causal, scale, dq=None, dk=None, dv=None, b
           v.stride(0), v.stride(1), v.stride(2), dq.stride(0), dq.stride(1), dq.stride(2),
           dk.stride(0), dk.stride(1), dk.stride(2), dv.stride(0), dv.stride(1), dv.stride(2)]
     L.flash_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(do), o_arg, _ptr(lse), _ptr(delta), _ptr(dq), _ptr(dk),
-                _ptr(dv), ds_arg, B, H, Sq, Sk, D, st, float(scale), int(causal), _dt(q), _stream(), bs_arg)
+                _ptr(dv), ds_arg, B, H, Sq, Sk, D, st, float(scale), int(causal), _dt(q), bs_arg, _stream())
     return (dq, dk, dv, bool(bs_arg)) if bsum is not None else (dq, dk, dv)
 
 
@@ -1551,8 +1556,8 @@ def _fa_ext_backward(ctx, do, outs=None, bsum=None):
                     _ptr(dv), _ptr(ds), B, H, Sq, Sk, D, gst, float(scale), int(causal), _dt(q),
                     _ptr(cu_q) if varlen else 0, _ptr(cu_k) if varlen else 0,
                     _ptr(mk) if mmeta is not None else 0, msb, msh, msq, int(m32), float(p_drop),
-                    int(seed), int(offset), _ptr(dbits) if dbits.numel() else 0, 0, _stream(),
-                    _ptr(bsum) if (bsum is not None and not varlen and Sq == Sk) else 0)
+                    int(seed), int(offset), _ptr(dbits) if dbits.numel() else 0, 0,
+                    _ptr(bsum) if (bsum is not None and not varlen and Sq == Sk) else 0, _stream())
     return dq, dk, dv
 
 
@@ -3009,16 +3014,16 @@ def _adamw_mt_hip(tab, ftab, ch, nch, lr, b1, b2, eps, bc1, bc2, grad_scale, sca
     """Multi-tensor AdamW over a device pointer table (one launch for every parameter);
     returns ``outs`` (the updated fp32 masters / params) so the NaN/Inf checker sees them."""
     _native.lib().adamw_mt(_ptr(tab), _ptr(ftab), _ptr(ch), nch, float(lr), float(b1), float(b2),
-                           float(eps), float(bc1), float(bc2), float(grad_scale), _stream(),
-                           0 if scale_t is None else _ptr(scale_t))
+                           float(eps), float(bc1), float(bc2), float(grad_scale),
+                           0 if scale_t is None else _ptr(scale_t), _stream())
     return outs
 
 
 @R.register_kernel('momentum_mt', 'hip')
 def _momentum_mt_hip(tab, ftab, ch, nch, lr, mu, nesterov, grad_scale, scale_t, outs):
     _native.lib().momentum_mt(_ptr(tab), _ptr(ftab), _ptr(ch), nch, float(lr), float(mu),
-                              int(nesterov), float(grad_scale), _stream(),
-                              0 if scale_t is None else _ptr(scale_t))
+                              int(nesterov), float(grad_scale),
+                              0 if scale_t is None else _ptr(scale_t), _stream())
     return outs
 
 
@@ -3402,10 +3407,11 @@ class MaxPoolNHWCFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         idx, = ctx.saved_tensors
-        n, h, w, c = ctx.geo[:4]
+        n, h, w, c, ho, wo, kh, kw, sh, sw, ph, pw = ctx.geo
         dy = dy.contiguous()
         dx = torch.empty((n, h, w, c), device=dy.device, dtype=dy.dtype)
-        _native.lib().max_pool_bwd(dy.data_ptr(), idx.data_ptr(), dx.data_ptr(), *ctx.geo, _dt(dy), _stream())
+        _native.lib().max_pool_bwd(dy.data_ptr(), idx.data_ptr(), dx.data_ptr(), n, h, w, c, ho, wo, kh, kw, sh,
+                                   sw, ph, pw, _dt(dy), _stream())
         return dx, None, None, None, None, None, None
 
 

@@ -215,6 +215,52 @@ def test_adamw_multi_tensor(master):
             assert torch.allclose(a, b, atol=1e-5)
 
 
+def _two_tensors():
+    """Two fp32 parameter tensors, the second crossing _mt_table's 65,536-element chunk."""
+    torch.manual_seed(0)
+    shapes = [(1000,), (70000,)]
+    return ([torch.randn(s, device=DEV) for s in shapes], [torch.randn(s, device=DEV) for s in shapes],
+            [0.1, 0.0])
+
+
+def test_adamw_multi_tensor_device_grad_scale():
+    """The clip coefficient read in-kernel from a device scalar (the gscale_ptr argument of the
+    entry, which sits next to the stream): one step against adamw_ref with the same factor."""
+    ps, gs, wds = _two_tensors()
+    ms, vs = [torch.zeros_like(p) for p in ps], [torch.zeros_like(p) for p in ps]
+    ref_p, ref_m, ref_v = [p.clone() for p in ps], [m.clone() for m in ms], [v.clone() for v in vs]
+    scale = torch.tensor(0.25, device=DEV)
+    mt = F.MultiTensorAdamW(ps, lambda: gs, ms, vs, [None, None], wds, [1.0, 1.0])
+    R.reset_stats()
+    mt.step(1e-2, 0.9, 0.999, 1e-8, 1, grad_scale=0.5, scale_tensor=scale)
+    assert R.stats().get(('adamw_mt', 'hip'), 0) == 1
+    F.adamw_ref(ref_p, gs, ref_m, ref_v, [None, None], 1e-2, 0.9, 0.999, 1e-8, wds, [1.0, 1.0], 1, 0.5 * 0.25)
+    torch.cuda.synchronize()
+    for got, ref in ((ps, ref_p), (ms, ref_m), (vs, ref_v)):
+        for a, b in zip(got, ref):
+            assert torch.allclose(a, b, atol=1e-5)
+
+
+@pytest.mark.parametrize('nesterov', [False, True])
+def test_momentum_multi_tensor_device_grad_scale(nesterov):
+    ps, gs, wds = _two_tensors()
+    vels = [torch.randn_like(p) for p in ps]
+    ref_p, ref_v = [p.clone() for p in ps], [v.clone() for v in vels]
+    scale = torch.tensor(0.25, device=DEV)
+    n = [p.numel() for p in ps]
+    cols = [[p.data_ptr() for p in ps], [g.data_ptr() for g in gs], [v.data_ptr() for v in vels], [0, 0], [0, 0],
+            n, [F._DT[g.dtype] for g in gs], [F._DT[p.dtype] for p in ps]]
+    tab, ftab, ch, nch = F._mt_table(cols, n, [wds, [1.0, 1.0]], ps[0].device)
+    R.reset_stats()
+    R.dispatch('momentum_mt', tab, tab, ftab, ch, nch, 1e-2, 0.9, nesterov, 0.5, scale, ps)
+    assert R.stats().get(('momentum_mt', 'hip'), 0) == 1
+    F.momentum_ref(ref_p, gs, ref_v, [None, None], 1e-2, 0.9, wds, nesterov, 0.5 * 0.25)
+    torch.cuda.synchronize()
+    for got, ref in ((ps, ref_p), (vels, ref_v)):
+        for a, b in zip(got, ref):
+            assert torch.allclose(a, b, atol=1e-5)
+
+
 def test_sumsq():
     ts = [torch.randn(1000, device=DEV), torch.randn(77, 3, device=DEV).bfloat16()]
     got = F.global_l2_norm_sq(ts)
