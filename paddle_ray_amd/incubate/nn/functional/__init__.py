@@ -211,6 +211,25 @@ def _ones_zeros(t, n, like):
                                      else None)
 
 
+def _scatter_paged(pool, tables, k, v):
+    """Positions [0, T) of every sequence written into the block pool [2, NB, KVH, BS, D] through
+    ``tables`` [B, MB]: k / v are [B, KVH, T, D] in the pool's dtype. Positions whose entry is
+    outside [0, NB) (``-1``: no block) or past the table are not written."""
+    NB, BS = pool.shape[1], pool.shape[3]
+    B, T = k.shape[0], k.shape[2]
+    tab = torch.as_tensor(tables).to(device=pool.device, dtype=torch.long)
+    if tab.dim() != 2 or tab.shape[0] != B:
+        raise ValueError(f"fused_multi_transformer: block_tables {tuple(tab.shape)} for batch {B}")
+    pos = torch.arange(T, device=pool.device)
+    col = pos // BS
+    blk = tab[:, col.clamp(max=tab.shape[1] - 1)]                 # [B, T]
+    valid = (blk >= 0) & (blk < NB) & (col < tab.shape[1])[None]
+    bi, pi = valid.nonzero(as_tuple=True)
+    dst, off = blk[bi, pi], pos[pi] % BS
+    pool[0, dst, :, off] = k.transpose(1, 2)[bi, pi].to(pool.dtype)
+    pool[1, dst, :, off] = v.transpose(1, 2)[bi, pi].to(pool.dtype)
+
+
 def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, linear_weights,
                             linear_biases, ffn_ln_scales, ffn_ln_biases, ffn1_weights, ffn1_biases,
                             ffn2_weights, ffn2_biases, pre_layer_norm=True, epsilon=1e-05,
@@ -220,7 +239,8 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
                             trans_qkvw=True, ring_id=-1, name=None, gqa_group_size=-1,
                             cache_k_quant_scales=None, cache_v_quant_scales=None,
                             cache_k_dequant_scales=None, cache_v_dequant_scales=None,
-                            quant_round_type=1, quant_max_bound=127.0, quant_min_bound=-127.0):
+                            quant_round_type=1, quant_max_bound=127.0, quant_min_bound=-127.0,
+                            block_tables=None):
     """N transformer layers for inference / generation (parity: reference
     incubate/nn/functional/fused_transformer.py:872 and fused_multi_transformer_op.cu.h).
 
@@ -249,6 +269,14 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
       The context phase stores the quantised K/V of the prompt, any ``pre_caches`` prefix
       included, while its own attention uses the unquantised K/V; the decode phase hands the
       scales to the decode kernel, which reads the bytes and appends the quantised token.
+    * paged KV cache: with ``block_tables`` ([B, MB] integers, ``-1`` for no block) every
+      ``cache_kvs[i]`` is a block pool [2, NB, KVH, BS, D] (float or ``uint8``) that the
+      sequences share; entry ``j`` of row ``b`` is the physical block of sequence ``b``'s logical
+      positions [j*BS, (j+1)*BS) (``ops.fused.mmha_decode``). The decode phase hands the table
+      to the decode kernel. The context phase writes positions [0, P+S) of every sequence
+      through the table, one indexed scatter per plane; a position whose entry is outside
+      [0, NB) is not written, and its own attention is unchanged. The pool is not indexed by
+      batch, so a call may carry any subset of the sequences with their table rows.
     * every residual add + dropout + following LayerNorm is ONE add_dropout_layer_norm
       kernel; FFN1 runs with its bias+activation in the GEMM epilogue.
     Returns ``out`` or ``(out, cache_kvs)`` when caches are given (updated in place)."""
@@ -262,8 +290,11 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
     KVH = int(gqa_group_size) if gqa_group_size is not None and int(gqa_group_size) > 0 else 0
     if decode and not isinstance(time_step, int):
         ts = _u(time_step)
-        # a device int32 step stays on the device (graph-capturable decode); host -> int
-        t = ts.reshape(-1)[:1] if (ts.is_cuda and ts.dtype == torch.int32) else int(ts.reshape(-1)[0])
+        # a device int32 step stays on the device (graph-capturable decode); host -> int. With
+        # block_tables an int32 tensor stays a tensor on the CPU too: a device-style position,
+        # so that a released slot's parked position is guarded instead of refused
+        t = ts.reshape(-1)[:1] if (ts.dtype == torch.int32 and (ts.is_cuda or block_tables is not None)) \
+            else int(ts.reshape(-1)[0])
     else:
         t = int(time_step) if decode else None
     if decode and S != 1:
@@ -306,6 +337,10 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
                 k = _rotary(qkv[:, :, 1], rot[0], rot[1], rotary_emb_dims)
                 qkv = torch.stack([q, k, qkv[:, :, 2]], 2)
         cache = _u(cache_kvs[i]) if cache_kvs is not None else None
+        if block_tables is not None and (cache is None or cache.dim() != 5):
+            raise ValueError(f"fused_multi_transformer: block_tables needs cache_kvs that are block "
+                             f"pools [2, NB, KVH, BS, D]; cache {i} is "
+                             f"{None if cache is None else tuple(cache.shape)}")
         if KVH and cache is not None and (cache.dim() != 5 or cache.shape[2] != KVH):
             raise ValueError(f"fused_multi_transformer: cache {i} is {tuple(cache.shape)}, "
                              f"gqa_group_size={KVH} needs [2, B, {KVH}, max_len, D]")
@@ -324,8 +359,9 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
             if cache is None:
                 raise ValueError("fused_multi_transformer: time_step needs cache_kvs")
             o = K.mmha_decode(qkv[:, 0].contiguous(), cache, t, mask, seq_lens=sl, rotary=krot,
-                              rotary_dims=rotary_emb_dims if krot is not None else 0, **qkw
-                              ).reshape(B, 1, H * D)
+                              rotary_dims=rotary_emb_dims if krot is not None else 0,
+                              **({} if block_tables is None else {'block_tables': _t(block_tables)}),
+                              **qkw).reshape(B, 1, H * D)
         else:
             if KVH:
                 q, k, v = qkv[:, :, :H], qkv[:, :, H:H + KVH], qkv[:, :, H + KVH:]
@@ -341,7 +377,13 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
                                      qkw['cache_k_dequant_scales'], qkw['cache_v_dequant_scales'],
                                      quant_round_type, quant_max_bound, quant_min_bound,
                                      h.device) if qkw else None
-            if quant is not None:                    # the bytes the decode kernel reads back
+            if block_tables is not None:             # through the table, one scatter per plane
+                kw_, vw_ = k.transpose(1, 2), v.transpose(1, 2)
+                if quant is not None:
+                    kw_ = K.kv_quantize(kw_, quant[0][0], *quant[2:])
+                    vw_ = K.kv_quantize(vw_, quant[0][1], *quant[2:])
+                _scatter_paged(cache, _t(block_tables), kw_, vw_)
+            elif quant is not None:                  # the bytes the decode kernel reads back
                 cache[0, :, :, :P + S] = K.kv_quantize(k.transpose(1, 2), quant[0][0], *quant[2:])
                 cache[1, :, :, :P + S] = K.kv_quantize(v.transpose(1, 2), quant[0][1], *quant[2:])
             elif cache is not None:

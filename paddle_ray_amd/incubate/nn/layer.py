@@ -143,7 +143,10 @@ class FusedMultiTransformer(Layer):
     ``uint8`` caches are the 8-bit KV cache: ``forward`` then takes the per-layer lists
     ``cache_k_quant_scales`` / ``cache_v_quant_scales`` (fp32 [KVH], or [B, KVH] per sequence;
     optional ``cache_*_dequant_scales``) and ``quant_round_type`` / ``quant_max_bound`` /
-    ``quant_min_bound``, as ``fused_multi_transformer`` does."""
+    ``quant_min_bound``, as ``fused_multi_transformer`` does.
+    ``block_tables`` ([B, MB] integers, ``-1`` for no block) makes ``caches`` block pools
+    [2, NB, KVH, BS, D] shared by the sequences: the context phase writes the prompt through the
+    table and a decode step reads and appends through it (``fused_multi_transformer``)."""
 
     def __init__(self, embed_dim, num_heads, dim_feedforward, dropout_rate=0.0, activation="gelu",
                  normalize_before=True, ln_scale_attrs=None, ln_bias_attrs=None,
@@ -204,7 +207,8 @@ class FusedMultiTransformer(Layer):
     def forward(self, src, attn_mask=None, caches=None, pre_caches=None, rotary_embs=None,
                 rotary_emb_dims=0, seq_lens=None, time_step=None, cache_k_quant_scales=None,
                 cache_v_quant_scales=None, cache_k_dequant_scales=None, cache_v_dequant_scales=None,
-                quant_round_type=1, quant_max_bound=127.0, quant_min_bound=-127.0):
+                quant_round_type=1, quant_max_bound=127.0, quant_min_bound=-127.0,
+                block_tables=None):
         return FF.fused_multi_transformer(
             src, self.ln_scales, self.ln_biases, self.qkv_weights, self.qkv_biases,
             self.linear_weights, self.linear_biases, self.ffn_ln_scales, self.ffn_ln_biases,
@@ -217,7 +221,8 @@ class FusedMultiTransformer(Layer):
             cache_k_quant_scales=cache_k_quant_scales, cache_v_quant_scales=cache_v_quant_scales,
             cache_k_dequant_scales=cache_k_dequant_scales,
             cache_v_dequant_scales=cache_v_dequant_scales, quant_round_type=quant_round_type,
-            quant_max_bound=quant_max_bound, quant_min_bound=quant_min_bound)
+            quant_max_bound=quant_max_bound, quant_min_bound=quant_min_bound,
+            block_tables=block_tables)
 
 
 class FusedMultiTransformerDecoder:
@@ -249,10 +254,28 @@ class FusedMultiTransformerDecoder:
     (``self.kv_scales``, per layer fp32 [4, Bs, KVH] = k quant, v quant, k dequant, v dequant)
     that ``prefill`` fills before the graph is captured, so the one graph keeps serving every
     step. A dynamic ``prefill`` holds the prompt's K/V in the model dtype until it has the scales.
+
+    Paged KV cache: ``block_size=BS`` replaces the per-slot ``max_seq_len`` rows by one block
+    pool per layer, ``self.caches[i]`` [2, num_blocks, KVH, BS, D] (float or ``uint8``), shared by
+    all slots through one persistent device table ``self.tables`` [B, MB] int32
+    (``MB = ceil(max_seq_len / BS)``, ``-1`` = no block; ``num_blocks`` defaults to ``B * MB``,
+    a smaller pool serves batches that never need every row at once). Blocks come from a host
+    free list: ``prefill`` gives sequence ``b`` ``ceil(len_b / BS)`` blocks, and ``step`` gives a
+    slot a new block when its position (a host mirror of ``self.lens``; the only sync is one in
+    ``prefill`` for device ``seq_lens``) reaches a block boundary, by a small write into the
+    table outside the graph, so the captured graph is never re-captured. ``free_blocks`` is the
+    number of free blocks; a ``step`` or ``prefill`` that needs more raises ``RuntimeError``
+    before it changes anything. Paged mode always runs the per-sequence (ragged) graph.
+    Continuous batching: ``release(b)`` returns slot ``b``'s blocks, clears its table row and
+    parks its position at ``MB * BS``, where the kernel's guard gives zeros and writes nothing;
+    ``admit(b, x)`` (x [1, S, E]) allocates blocks, runs the context phase for that one prompt
+    through table row ``b`` and sets the slot's position to ``S`` (and, with dynamic int8
+    scales, the slot's scales from its prompt), leaving the other slots and the graph alone.
+    On the GPU ``BS`` must be a power of two >= 16.
     """
 
     def __init__(self, model, batch_size, max_seq_len, use_graph=True, kv_cache_dtype=None,
-                 cache_scales=None):
+                 cache_scales=None, block_size=None, num_blocks=None):
         import torch
         self.model = model
         self.B, self.L = int(batch_size), int(max_seq_len)
@@ -291,14 +314,29 @@ class FusedMultiTransformerDecoder:
             self._qkw = {name: [pick(s, j) for s in self.kv_scales] for j, name in enumerate(
                 ('cache_k_quant_scales', 'cache_v_quant_scales', 'cache_k_dequant_scales',
                  'cache_v_dequant_scales'))}
+        self.paged = block_size is not None
+        if num_blocks is not None and not self.paged:
+            raise ValueError("FusedMultiTransformerDecoder: num_blocks goes with block_size")
+        shape = (2, self.B, KVH, self.L, D)
+        if self.paged:
+            self.BS = int(block_size)
+            if self.BS < 1:
+                raise ValueError(f"FusedMultiTransformerDecoder: block_size must be >= 1, got {block_size}")
+            self.MB = -(-self.L // self.BS)
+            self.NB = self.B * self.MB if num_blocks is None else int(num_blocks)
+            if self.NB < 1:
+                raise ValueError(f"FusedMultiTransformerDecoder: num_blocks must be >= 1, got {num_blocks}")
+            shape = (2, self.NB, KVH, self.BS, D)
+            self.tables = torch.full((self.B, self.MB), -1, dtype=torch.int32, device=self.dev)
+            self._free = list(range(self.NB - 1, -1, -1))       # popped from the end: block 0 first
+            self._blocks = [[] for _ in range(self.B)]           # host: each slot's blocks, in order
+            self._pos = [0] * self.B                             # host mirror of self.lens; None: released
         # a uint8 cache starts at the byte of level 0
-        self.caches = [torch.full((2, self.B, KVH, self.L, D), 128, device=self.dev, dtype=torch.uint8)
-                       if self.q8 else
-                       torch.zeros(2, self.B, KVH, self.L, D, device=self.dev, dtype=self.dtype)
-                       for _ in range(n)]
+        self.caches = [torch.full(shape, 128, device=self.dev, dtype=torch.uint8) if self.q8 else
+                       torch.zeros(shape, device=self.dev, dtype=self.dtype) for _ in range(n)]
         self.t = torch.zeros(1, dtype=torch.int32, device=self.dev)
         self.lens = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
-        self.ragged = False
+        self.ragged = self.paged      # paged mode: always the per-sequence graph
         self.rot = None               # [2, max_seq_len, D] fp32 (cos, sin)
         self.rot_dims = 0
         self.mask = torch.zeros(self.B, 1, 1, self.L, dtype=torch.float32, device=self.dev)
@@ -347,6 +385,9 @@ class FusedMultiTransformerDecoder:
             sl = seq_lens._t if hasattr(seq_lens, '_t') else torch.as_tensor(seq_lens)
             sl = sl.reshape(self.B).to(device=self.dev, dtype=torch.int32)
             kw['seq_lens'] = Tensor(sl)
+        if self.paged:
+            self._assign([int(n) for n in sl.tolist()] if ragged else [S0] * self.B)
+            kw['block_tables'] = Tensor(self.tables)
         with torch.no_grad():
             if self.dynamic_scales:
                 # the prompt's K/V in the model dtype first: their absmax gives the scales
@@ -354,7 +395,7 @@ class FusedMultiTransformerDecoder:
                 tmp = [torch.zeros(2, self.B, KVH, S0, D, device=self.dev, dtype=self.dtype)
                        for _ in self.caches]
                 out, _ = self.model(Tensor(xt), attn_mask=attn_mask, caches=[Tensor(c) for c in tmp],
-                                    **kw)
+                                    **{k: v for k, v in kw.items() if k != 'block_tables'})
                 self._quantize_prompt(tmp, sl if ragged else None)
             else:
                 out, _ = self.model(Tensor(xt), attn_mask=attn_mask, caches=self._caches(), **kw,
@@ -365,16 +406,118 @@ class FusedMultiTransformerDecoder:
         else:
             self.lens.fill_(S0)
             self.t.fill_(S0)
-        if ragged != self.ragged:
+        if not self.paged and ragged != self.ragged:
             self.ragged, self._graph = ragged, None      # the other graph
         return out
 
-    def _quantize_prompt(self, kv, seq_lens):
+    # ------------------------------------------------------------------ paged mode
+    @property
+    def free_blocks(self):
+        """Number of blocks on the free list (paged mode)."""
+        return len(self._free)
+
+    def _need_paged(self, what):
+        if not self.paged:
+            raise RuntimeError(f"FusedMultiTransformerDecoder.{what} needs paged mode (block_size=...)")
+
+    def _set_row(self, b, blocks):
+        """Slot ``b``'s blocks on the host and its table row on the device (the rest -1)."""
+        import torch
+        self._blocks[b] = list(blocks)
+        row = torch.full((self.MB,), -1, dtype=torch.int32)
+        row[:len(blocks)] = torch.tensor(blocks, dtype=torch.int32)
+        self.tables[b].copy_(row)
+
+    def _assign(self, lens):
+        """A fresh batch: every block back on the free list, then ``ceil(len_b / BS)`` blocks for
+        each sequence. Raises before it changes anything when the pool is too small."""
+        need = [-(-n // self.BS) for n in lens]
+        if any(not 0 <= n <= self.MB * self.BS for n in lens):
+            raise ValueError(f"FusedMultiTransformerDecoder: prompt lengths {lens} outside "
+                             f"[0, {self.MB * self.BS}]")
+        if sum(need) > self.NB:
+            raise RuntimeError(f"FusedMultiTransformerDecoder: the prompts need {sum(need)} blocks of "
+                               f"{self.BS}, the pool has {self.NB}")
+        self._free = list(range(self.NB - 1, -1, -1))
+        for b, k in enumerate(need):
+            self._set_row(b, [self._free.pop() for _ in range(k)])
+        self._pos = list(lens)
+
+    def _grow(self):
+        """Before a step: a live slot whose position starts a block it does not have yet gets one,
+        written into the device table outside the graph. Raises before it changes anything."""
+        want = [b for b, p in enumerate(self._pos)
+                if p is not None and p < self.L and p // self.BS >= len(self._blocks[b])]
+        if len(want) > len(self._free):
+            raise RuntimeError(f"FusedMultiTransformerDecoder: {len(want)} slots need a new block and "
+                               f"{len(self._free)} are free; release a slot or use a larger pool")
+        for b in want:
+            e = self._free.pop()
+            self.tables[b, len(self._blocks[b])].fill_(e)
+            self._blocks[b].append(e)
+
+    def release(self, b):
+        """Slot ``b`` leaves the batch: its blocks go back to the free list, its table row to -1
+        and its position to ``MB * BS``, where every later step gives it zeros and writes nothing."""
+        self._need_paged('release')
+        b = int(b)
+        self._free.extend(reversed(self._blocks[b]))
+        self._set_row(b, [])
+        self.lens[b].fill_(self.MB * self.BS)
+        self._pos[b] = None
+
+    def admit(self, b, x, attn_mask=None):
+        """A new prompt ``x`` [1, S, E] joins the running batch in the released (or unused) slot
+        ``b``: blocks are allocated, the context phase runs for this one sequence through table
+        row ``b`` and the slot continues at position ``S``. Returns the prompt's output
+        [1, S, E]; the other slots and the captured step graph are untouched."""
+        from ...framework.core import Tensor
+        import torch
+        self._need_paged('admit')
+        b = int(b)
+        xt = x._t if hasattr(x, '_t') else x
+        S = xt.shape[1]
+        if xt.shape[0] != 1 or not 0 < S <= self.L:
+            raise ValueError(f"FusedMultiTransformerDecoder.admit: x must be [1, S, E] with "
+                             f"0 < S <= {self.L}, got {tuple(xt.shape)}")
+        if self._blocks[b]:
+            raise RuntimeError(f"FusedMultiTransformerDecoder.admit: slot {b} holds a sequence; "
+                               "release it first")
+        need = -(-S // self.BS)
+        if need > len(self._free):
+            raise RuntimeError(f"FusedMultiTransformerDecoder.admit: the prompt needs {need} blocks "
+                               f"and {len(self._free)} are free")
+        self._set_row(b, [self._free.pop() for _ in range(need)])
+        if attn_mask is None:
+            m = torch.triu(torch.full((S, S), float('-inf'), device=self.dev), 1)
+            attn_mask = Tensor(m.expand(1, 1, S, S).to(self.dtype))
+        kw = dict(block_tables=Tensor(self.tables[b:b + 1]))
+        if self.rot is not None:
+            r = self.rot[:, :S]
+            kw.update(rotary_embs=Tensor(r[:, None, None]), rotary_emb_dims=self.rot_dims)
+        with torch.no_grad():
+            if self.dynamic_scales:
+                KVH, D = self.caches[0].shape[2], self.caches[0].shape[4]
+                tmp = [torch.zeros(2, 1, KVH, S, D, device=self.dev, dtype=self.dtype) for _ in self.caches]
+                out = self.model(Tensor(xt), attn_mask=attn_mask, caches=[Tensor(c) for c in tmp],
+                                 **{k: v for k, v in kw.items() if k != 'block_tables'})[0]
+                self._quantize_prompt(tmp, None, slot=b)
+            else:
+                out, _ = self.model(Tensor(xt), attn_mask=attn_mask, caches=self._caches(), **kw,
+                                    **self._qkw)
+        self.lens[b].fill_(S)
+        self.t.copy_(torch.clamp(self.t, min=S))
+        self._pos[b] = S
+        return out
+
+    def _quantize_prompt(self, kv, seq_lens, slot=None):
         """Dynamic scales from the prompt's K/V (``kv``: per layer [2, B, KVH, S0, D], K after
         rotary) over each sequence's valid positions, written into ``self.kv_scales``; then
-        the quantised prompt into the uint8 caches."""
+        the quantised prompt into the uint8 caches (paged: through the table). ``slot``: ``kv``
+        holds that one slot's prompt (batch 1) and only its scales and blocks are written."""
         import torch
         from ...ops import fused as K
+        rows = slice(None) if slot is None else slice(slot, slot + 1)
         S0 = kv[0].shape[3]
         pad = None
         if seq_lens is not None:
@@ -386,19 +529,28 @@ class FusedMultiTransformerDecoder:
                 a = a.masked_fill(pad, 0.0)
             a = a.amax(dim=(3, 4))                            # [2, B, KVH]
             q = torch.where(a > 0, 127.0 / a, torch.ones_like(a))
-            s[:2].copy_(q)
-            s[2:].copy_(1.0 / q)
-            c[0, :, :, :S0] = K.kv_quantize(x[0], s[0])
-            c[1, :, :, :S0] = K.kv_quantize(x[1], s[1])
+            s[:2, rows].copy_(q)
+            s[2:, rows].copy_(1.0 / q)
+            if self.paged:
+                FF._scatter_paged(c, self.tables[rows], K.kv_quantize(x[0], s[0, rows]),
+                                  K.kv_quantize(x[1], s[1, rows]))
+            else:
+                c[0, :, :, :S0] = K.kv_quantize(x[0], s[0])
+                c[1, :, :, :S0] = K.kv_quantize(x[1], s[1])
 
     def _step_eager(self):
         from ...framework.core import Tensor
         kw = dict(self._qkw)
         if self.ragged:
             kw['seq_lens'] = Tensor(self.lens)
+        if self.paged:
+            kw['block_tables'] = Tensor(self.tables)
         if self.rot is not None:
             # every sequence's own row: its position when ragged, else the common one
-            r = self.rot.index_select(1, self.lens if self.ragged else self.t)
+            pos = self.lens if self.ragged else self.t
+            if self.paged:            # a released slot is parked past the tables: any row will do
+                pos = pos.clamp(max=self.L - 1)
+            r = self.rot.index_select(1, pos)
             r = r.expand(2, self.B, r.shape[-1])
             kw.update(rotary_embs=Tensor(r[:, :, None, None]), rotary_emb_dims=self.rot_dims)
         out, _ = self.model(Tensor(self.x_buf), attn_mask=Tensor(self.mask), caches=self._caches(),
@@ -415,6 +567,9 @@ class FusedMultiTransformerDecoder:
         import torch
         from ...framework.core import Tensor
         xt = x_tok._t if hasattr(x_tok, '_t') else x_tok
+        if self.paged:                # blocks first: an exhausted pool raises with nothing changed
+            self._grow()
+            self._pos = [p if p is None else p + 1 for p in self._pos]
         self.x_buf.copy_(xt.reshape(self.x_buf.shape))
         with torch.no_grad():
             if not self.use_graph:

@@ -105,6 +105,10 @@ PYBIND11_MODULE(_pra_hip, m) {
   Launch<&pra_mmha_decode>::def(m, "mmha_decode",
                                 "unsupported head_dim/group ratio/dtype/rotary_dims/quantisation arguments for a "
                                 "uint8 cache, or time_step out of range");
+  // the same step over a block pool [2, NB, KVH, BS, D] and an int32 block table [B, MB]
+  Launch<&pra_mmha_decode_paged>::def(m, "mmha_decode_paged",
+                                      "block size not a power of two >= 16, null block table, or anything "
+                                      "mmha_decode refuses at L = MB*BS");
   Launch<&pra_bias_gelu_fwd>::def(m, "bias_gelu_fwd");
   Launch<&pra_bias_gelu_bwd>::def(m, "bias_gelu_bwd");
   Launch<&pra_bias_gelu_bwd_db>::def(m, "bias_gelu_bwd_db");

@@ -53,6 +53,19 @@
 //    workspace and mmha_combine_k see ordinary partials. The new token's K (rotated in fp32,
 //    not rounded to T) and V are quantised in registers with one fp32 multiply and one
 //    rounding, appended as one 8-byte vector store per lane, and scored as those levels.
+//  * paged cache (PAGED instantiations, always EXT; a contiguous-cache one is compiled without
+//    any of it): the cache is a block pool [2, NB, KVH, BS, D] (the K plane, then the V plane)
+//    and block_tables [B, MB] int32 names, for sequence b, the physical block of logical
+//    positions [j*BS, (j+1)*BS); BS is a power of two >= 16 given as a shift. Everything above
+//    keeps working on logical positions with L = MB*BS; only the row address changes: key p of
+//    K/V head kvh is row (table[b][p >> shift] * KVH + kvh) * BS + (p & (BS - 1)) of a plane.
+//    Table entries are untrusted: an entry outside [0, NB) never becomes an address. A key in
+//    such a block scores -inf and its loads go to the token's own row (whose block the guard
+//    has checked; the loop's usual fallback row lo may itself lie in a bad block), and a
+//    sequence whose own block is bad is guarded like one whose position is out of range. The
+//    16-byte row loads depend on a 4-byte table load, so the entries of the next iteration's
+//    keys are fetched one iteration ahead, after this iteration's row loads are issued and
+//    before its math: as many row bytes stay in flight per lane as without paging.
 #include <type_traits>
 
 #include "common.h"
@@ -149,10 +162,26 @@ __device__ __forceinline__ void unpack8(uint2 w, float* o) {
   }
 }
 
-template <typename T, int D, int R, bool EXT, bool Q8>
+// what only a PAGED instantiation is given (an empty parameter otherwise)
+template <bool PAGED> struct PParams {};
+template <> struct PParams<true> {
+  const int* tables;  // [B, MB] int32 physical block per logical block, untrusted
+  int NB, MB, shift;  // pool blocks, table columns, log2 of the block size
+};
+
+__device__ __forceinline__ size_t pool_plane(const PParams<false>&, int) { return 0; }
+__device__ __forceinline__ size_t pool_plane(const PParams<true>& pp, int KVH) {  // rows of one plane
+  return ((size_t)pp.NB * KVH) << pp.shift;
+}
+
+// one kernel parameter for both: empty bases take no room, so a (Q8, false) instantiation is
+// given exactly what it was given before there were pages
+template <bool Q8, bool PAGED> struct XParams : QParams<Q8>, PParams<PAGED> {};
+
+template <typename T, int D, int R, bool EXT, bool Q8, bool PAGED>
 __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
     const T* __restrict__ qkv,      // [B, H + 2*KVH, D] (bias already added)
-    std::conditional_t<Q8, uint8_t, T>* __restrict__ cache,  // [2, B, KVH, L, D]
+    std::conditional_t<Q8, uint8_t, T>* __restrict__ cache,  // [2, B, KVH, L, D]; PAGED: [2, NB, KVH, BS, D]
     const float* __restrict__ mask, // [B, mask_len] additive, or null
     float* __restrict__ ws_ml,      // [B, H, S, 2]
     float* __restrict__ ws_acc,     // [B, H, S, D]
@@ -161,8 +190,11 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
     float scale,
     const int* __restrict__ seq_lens,  // EXT: [B] per-sequence position, or null
     const float* __restrict__ rot,     // EXT: [2, B, D] cos then sin, or null
-    int rot_dims, QParams<Q8> qp) {
+    int rot_dims, XParams<Q8, PAGED> xp) {
   static_assert(EXT || !Q8, "the Q8 instantiations are EXT ones");
+  static_assert(EXT || !PAGED, "the PAGED instantiations are EXT ones");
+  [[maybe_unused]] const QParams<Q8>& qp = xp;
+  [[maybe_unused]] const PParams<PAGED>& pp = xp;
   using C = std::conditional_t<Q8, uint8_t, T>;  // a cache element
   // t_dev (HIP-graph decode loops): the position comes from device memory, so one captured
   // graph serves every step; an out-of-range position writes nothing and outputs zeros
@@ -182,7 +214,18 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
       in_bound = t_dev || t <= t_host;  // a device bound means the splits cover all of L
     }
   }
-  const bool t_ok = in_bound && t >= 0 && t < L && !(mask && mask_len < t + 1);
+  bool t_ok = in_bound && t >= 0 && t < L && !(mask && mask_len < t + 1);
+  // PAGED: this sequence's table row, the entry of the token's own block, and in-block mask
+  [[maybe_unused]] const int* tab = nullptr;
+  [[maybe_unused]] int et = 0, bmask = 0;
+  if constexpr (PAGED) {
+    tab = pp.tables + (size_t)b * pp.MB;
+    bmask = (1 << pp.shift) - 1;
+    if (t_ok) {  // t in [0, L): the column is inside the table row
+      et = tab[t >> pp.shift];
+      t_ok = (unsigned)et < (unsigned)pp.NB;
+    }
+  }
   const int lo = split * keys_per_split;
   const int hi = t_ok ? min(t + 1, lo + keys_per_split) : lo;
 
@@ -190,8 +233,9 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
   const T* qrow = qkv + ((size_t)b * rows + h0) * D;          // R consecutive query rows
   const T* knew = qkv + ((size_t)b * rows + H + kvh) * D;
   const T* vnew = knew + (size_t)KVH * D;
-  C* kc = cache + ((size_t)b * KVH + kvh) * (size_t)L * D;
-  C* vc = cache + (((size_t)B + b) * KVH + kvh) * (size_t)L * D;
+  // PAGED: the two planes; a row index below is then a plane row, not a position
+  C* kc = PAGED ? cache : cache + ((size_t)b * KVH + kvh) * (size_t)L * D;
+  C* vc = PAGED ? cache + pool_plane(pp, KVH) * D : cache + (((size_t)B + b) * KVH + kvh) * (size_t)L * D;
   const size_t w0 = ((size_t)b * H + h0) * splits + split;    // partial of query head h0; head r: + r*splits
 
   if (hi <= lo) {  // a key range past t, or a guarded position: no loads, R empty partials
@@ -207,6 +251,9 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
     return;
   }
 
+  // the row of position t (hi > lo here, so t_ok: PAGED, et is a block of the pool)
+  size_t trow = (size_t)t;
+  if constexpr (PAGED) trow = ((((size_t)et * KVH + kvh) << pp.shift) + (t & bmask));
   float q[R][8];
   float kt[8];  // the token's own k exactly as the cache holds it
 #pragma unroll
@@ -241,14 +288,14 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
     ktq = quant8(kt, sp[0], qp.round_type, qp.qmax, qp.qmin);
     vtq = quant8(vt, sp[plane], qp.round_type, qp.qmax, qp.qmin);
     if (t < hi && wave == 0 && grp == 0) {  // append: one 8-byte store per lane and row
-      *reinterpret_cast<uint2*>(kc + (size_t)t * D + gl * 8) = ktq;
-      *reinterpret_cast<uint2*>(vc + (size_t)t * D + gl * 8) = vtq;
+      *reinterpret_cast<uint2*>(kc + trow * D + gl * 8) = ktq;
+      *reinterpret_cast<uint2*>(vc + trow * D + gl * 8) = vtq;
     }
   } else if (t < hi && wave == 0 && grp == 0) {  // append the new token (hi > lo here, so t_ok and t >= lo)
     float v[8];
-    store8<T>(kc + (size_t)t * D + gl * 8, kt);
+    store8<T>(kc + trow * D + gl * 8, kt);
     load8<T>(vnew + gl * 8, v);
-    store8<T>(vc + (size_t)t * D + gl * 8, v);
+    store8<T>(vc + trow * D + gl * 8, v);
   }
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -280,20 +327,46 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
     // states of R = 8 leave registers for 2 (with 4 it drops to one wave per SIMD and spills)
     constexpr int U = R >= 8 ? 2 : 4;
     constexpr int STEP = kWaves * KPW * U;
+    [[maybe_unused]] int ent[U];  // PAGED: the table entries of this iteration's keys
+    if constexpr (PAGED) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int key = lo + (u * kWaves + wave) * KPW + grp;
+        ent[u] = tab[(key < hi ? key : lo) >> pp.shift];
+      }
+    }
     for (int base = lo; base < hi; base += STEP) {
       uint2 kr[U], vr[U];
       float add[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int key = base + (u * kWaves + wave) * KPW + grp;
-        const int kk = key < hi ? key : lo;
-        kr[u] = *reinterpret_cast<const uint2*>(kc + (size_t)kk * D + gl * 8);
-        vr[u] = *reinterpret_cast<const uint2*>(vc + (size_t)kk * D + gl * 8);
+        int kk = key < hi ? key : lo;
+        size_t row = (size_t)kk;
+        bool live = key < hi;
+        if constexpr (PAGED) {
+          int e = ent[u];
+          if ((unsigned)e >= (unsigned)pp.NB) {  // no address from it: the token's own row, weight 0
+            e = et;
+            kk = t;
+            live = false;
+          }
+          row = (((size_t)e * KVH + kvh) << pp.shift) + (kk & bmask);
+        }
+        kr[u] = *reinterpret_cast<const uint2*>(kc + row * D + gl * 8);
+        vr[u] = *reinterpret_cast<const uint2*>(vc + row * D + gl * 8);
         if (kk == t) {  // the token's own row: the quantised registers, not what the slot held
           kr[u] = ktq;
           vr[u] = vtq;
         }
-        add[u] = key < hi ? (mrow ? mrow[key] : 0.f) : -INFINITY;
+        add[u] = live ? (mrow ? mrow[key] : 0.f) : -INFINITY;
+      }
+      if constexpr (PAGED) {  // the next iteration's entries, behind this one's row loads
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int key = base + STEP + (u * kWaves + wave) * KPW + grp;
+          ent[u] = tab[(key < hi ? key : lo) >> pp.shift];
+        }
       }
       float pw[R][U], cr[R];
       {
@@ -339,14 +412,33 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
     }
   } else {
     constexpr int STEP = kWaves * KPW * 2;
+    [[maybe_unused]] int ent[2];  // PAGED: the table entries of this iteration's keys
+    if constexpr (PAGED) {
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int key = lo + (u * kWaves + wave) * KPW + grp;
+        ent[u] = tab[(key < hi ? key : lo) >> pp.shift];
+      }
+    }
     for (int base = lo; base < hi; base += STEP) {
       float kx[2][8], vx[2][8], add[2];
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const int key = base + (u * kWaves + wave) * KPW + grp;
-        const int kk = key < hi ? key : lo;
-        const T* kp = (kk == t) ? knew : kc + (size_t)kk * D;
-        const T* vp = (kk == t) ? vnew : vc + (size_t)kk * D;
+        int kk = key < hi ? key : lo;
+        size_t row = (size_t)kk;
+        bool live = key < hi;
+        if constexpr (PAGED) {
+          int e = ent[u];
+          if ((unsigned)e >= (unsigned)pp.NB) {  // no address from it: the token's own row, weight 0
+            e = et;
+            kk = t;
+            live = false;
+          }
+          row = (((size_t)e * KVH + kvh) << pp.shift) + (kk & bmask);
+        }
+        const T* kp = (kk == t) ? knew : kc + row * D;
+        const T* vp = (kk == t) ? vnew : vc + row * D;
         load8<T>(kp + gl * 8, kx[u]);
         load8<T>(vp + gl * 8, vx[u]);
         if constexpr (EXT) {  // the token's own key: the (rotated, rounded) registers, not the raw row
@@ -355,8 +447,16 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
             for (int i = 0; i < 8; ++i) kx[u][i] = kt[i];
           }
         }
-        // a key past the range scores -inf: its weight is exactly 0
-        add[u] = key < hi ? (mrow ? mrow[key] : 0.f) : -INFINITY;
+        // a key past the range (PAGED: or in a block the table does not give) scores -inf: its
+        // weight is exactly 0
+        add[u] = live ? (mrow ? mrow[key] : 0.f) : -INFINITY;
+      }
+      if constexpr (PAGED) {  // the next iteration's entries, behind this one's row loads
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const int key = base + STEP + (u * kWaves + wave) * KPW + grp;
+          ent[u] = tab[(key < hi ? key : lo) >> pp.shift];
+        }
       }
 #pragma unroll
       for (int r = 0; r < R; ++r) {
@@ -469,6 +569,8 @@ struct Args {
   const float* scales;  // 8-bit cache: [4, Bs, KVH], else null
   int scale_bstride, round_type;
   float qmax, qmin;
+  const int* tables;  // paged cache: [B, MB] int32, else null
+  int NB, MB, shift;
 };
 
 template <bool Q8> QParams<Q8> qparams(const Args& a);
@@ -477,16 +579,20 @@ template <> QParams<true> qparams<true>(const Args& a) {
   return {a.scales, a.scale_bstride, a.round_type, a.qmax, a.qmin};
 }
 
-template <typename T, int D, int R, bool EXT, bool Q8 = false>
+template <bool PAGED> PParams<PAGED> pparams(const Args& a);
+template <> PParams<false> pparams<false>(const Args&) { return {}; }
+template <> PParams<true> pparams<true>(const Args& a) { return {a.tables, a.NB, a.MB, a.shift}; }
+
+template <typename T, int D, int R, bool EXT, bool Q8 = false, bool PAGED = false>
 int launch(const Args& a) {
   const int keys = a.t_dev ? a.L : a.t + 1;  // device position: splits cover the whole cache
   const int per = (keys + a.splits - 1) / a.splits;
   float* ws_ml = a.ws;
   float* ws_acc = a.ws + (((size_t)a.B * a.H * a.splits * 2 + 3) / 4) * 4;  // 16-B aligned
-  hipLaunchKernelGGL((mmha_split_k<T, D, R, EXT, Q8>), dim3(a.splits, a.KVH, a.B), dim3(kWaves * 64), 0, a.s,
+  hipLaunchKernelGGL((mmha_split_k<T, D, R, EXT, Q8, PAGED>), dim3(a.splits, a.KVH, a.B), dim3(kWaves * 64), 0, a.s,
                      (const T*)a.qkv, (std::conditional_t<Q8, uint8_t, T>*)a.cache, a.mask, ws_ml, ws_acc, (T*)a.out,
                      a.B, a.KVH, a.L, a.t, a.t_dev, per, a.mask_len, a.scale, a.seq_lens, a.rot, a.rot_dims,
-                     qparams<Q8>(a));
+                     XParams<Q8, PAGED>{qparams<Q8>(a), pparams<PAGED>(a)});
   if (a.splits > 1)
     hipLaunchKernelGGL((mmha_combine_k<T, D>), dim3(a.H, a.B), dim3(D), 0, a.s, ws_ml, ws_acc, (T*)a.out, a.splits);
   return 0;
@@ -494,6 +600,15 @@ int launch(const Args& a) {
 
 template <typename T, int D>
 int launch_r(const Args& a) {
+  if (a.tables) {  // paged cache: EXT instantiations only, float and 8-bit pools
+    switch (a.H / a.KVH) {
+      case 1: return a.scales ? launch<T, D, 1, true, true, true>(a) : launch<T, D, 1, true, false, true>(a);
+      case 2: return a.scales ? launch<T, D, 2, true, true, true>(a) : launch<T, D, 2, true, false, true>(a);
+      case 4: return a.scales ? launch<T, D, 4, true, true, true>(a) : launch<T, D, 4, true, false, true>(a);
+      case 8: return a.scales ? launch<T, D, 8, true, true, true>(a) : launch<T, D, 8, true, false, true>(a);
+      default: return -1;
+    }
+  }
   if (a.scales) {  // 8-bit cache: EXT instantiations only
     switch (a.H / a.KVH) {
       case 1: return launch<T, D, 1, true, true>(a);
@@ -520,6 +635,27 @@ int launch_d(int D, const Args& a) {
     case 256: return launch_r<T, 256>(a);
     default: return -1;
   }
+}
+
+// the checks and the dispatch that the contiguous and the paged entry share (a.L is the
+// logical capacity either way)
+int decode(const Args& a, int D, int dt, int cache_dt) {
+  if (a.splits < 1 || a.B < 1 || a.B > 65535 || a.KVH < 1 || a.KVH > 65535 || a.H < a.KVH || a.H % a.KVH != 0 ||
+      a.L < 1)
+    return -1;
+  if (!a.t_dev && (a.t < 0 || a.t >= a.L || (a.mask && a.mask_len < a.t + 1))) return -1;
+  if (a.rot && (a.rot_dims < 1 || D % (16 * a.rot_dims) != 0)) return -1;  // a half chunk is whole 8-dim lanes
+  if (cache_dt == kCacheU8) {  // a row piece is one aligned 8-byte access
+    if (!a.scales || (a.scale_bstride != 0 && a.scale_bstride != a.KVH) || (a.round_type != 0 && a.round_type != 1) ||
+        !(a.qmin >= -128.f && a.qmin < a.qmax && a.qmax <= 127.f) || ((uintptr_t)a.cache & 7) != 0)
+      return -1;
+  } else if (cache_dt != dt || a.scales) {
+    return -1;
+  }
+  if (dt == kBF16) return launch_d<bf16>(D, a);
+  if (dt == kF16) return launch_d<f16>(D, a);
+  if (dt == kF32) return launch_d<float>(D, a);
+  return -1;
 }
 
 }  // namespace
@@ -553,21 +689,30 @@ int pra_mmha_decode(const void* qkv, void* cache, const float* mask, float* ws, 
                     int L, int D, int t, const int* t_dev, int splits, int mask_len, float scale, int dt,
                     const int* seq_lens, const float* rot, int rot_dims, hipStream_t s, int cache_dt,
                     const float* scales, int scale_batch_stride, int round_type, float qmax, float qmin) {
-  if (splits < 1 || B < 1 || B > 65535 || KVH < 1 || KVH > 65535 || H < KVH || H % KVH != 0 || L < 1) return -1;
-  if (!t_dev && (t < 0 || t >= L || (mask && mask_len < t + 1))) return -1;
-  if (rot && (rot_dims < 1 || D % (16 * rot_dims) != 0)) return -1;  // a half chunk is whole 8-dim lanes
-  if (cache_dt == kCacheU8) {  // a row piece is one aligned 8-byte access
-    if (!scales || (scale_batch_stride != 0 && scale_batch_stride != KVH) || (round_type != 0 && round_type != 1) ||
-        !(qmin >= -128.f && qmin < qmax && qmax <= 127.f) || ((uintptr_t)cache & 7) != 0)
-      return -1;
-  } else if (cache_dt != dt || scales) {
-    return -1;
-  }
   const Args a{qkv, cache, mask, ws, out, B, H, KVH, L, t, t_dev, splits, mask_len, scale, seq_lens, rot,
-               rot_dims, s, scales, scale_batch_stride, round_type, qmax, qmin};
-  if (dt == kBF16) return launch_d<bf16>(D, a);
-  if (dt == kF16) return launch_d<f16>(D, a);
-  if (dt == kF32) return launch_d<float>(D, a);
-  return -1;
+               rot_dims, s, scales, scale_batch_stride, round_type, qmax, qmin, nullptr, 0, 0, 0};
+  return decode(a, D, dt, cache_dt);
+}
+
+// The same step over a paged cache: cache is the block pool [2, NB, KVH, BS, D] (the K plane,
+// then the V plane; float or uint8 as above) and block_tables the device int32 [B, MB] table:
+// entry j of row b is the physical block of logical positions [j*BS, (j+1)*BS) of sequence b.
+// The logical capacity L = MB*BS takes the place of pra_mmha_decode's L in everything else
+// (t, t_dev, seq_lens, mask_len, splits from pra_mmha_splits). Entries are not trusted: one
+// outside [0, NB) is never made into an address; its keys carry weight 0, and a sequence whose
+// own position lies in such a block gets zeros and no write. Returns non-zero when BS is not a
+// power of two >= 16, block_tables is null, NB or MB < 1, MB*BS overflows, or for anything
+// pra_mmha_decode refuses with L = MB*BS.
+int pra_mmha_decode_paged(const void* qkv, void* cache, const float* mask, float* ws, void* out, int B, int H,
+                          int KVH, int NB, int BS, int MB, int D, int t, const int* t_dev, int splits,
+                          int mask_len, float scale, int dt, const int* seq_lens, const float* rot, int rot_dims,
+                          hipStream_t s, int cache_dt, const float* scales, int scale_batch_stride, int round_type,
+                          float qmax, float qmin, const int* block_tables) {
+  if (!block_tables || BS < 16 || (BS & (BS - 1)) != 0 || NB < 1 || MB < 1 || (long long)MB * BS > 0x7fffffffLL)
+    return -1;
+  const int shift = __builtin_ctz((unsigned)BS);
+  const Args a{qkv, cache, mask, ws, out, B, H, KVH, MB * BS, t, t_dev, splits, mask_len, scale, seq_lens, rot,
+               rot_dims, s, scales, scale_batch_stride, round_type, qmax, qmin, block_tables, NB, MB, shift};
+  return decode(a, D, dt, cache_dt);
 }
 }

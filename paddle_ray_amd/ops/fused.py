@@ -774,6 +774,9 @@ def vocab_parallel_cross_entropy(logits, labels, pg=None, world=1, rank=0, ignor
 # 8-bit cache (the same kernel template again): a uint8 cache of bytes level + 128 with fp32
 # quant / dequant scales per K/V head, [KVH] or per sequence [B, KVH]; kv_quantize and
 # kv_dequantize are the stored byte and the value read back, in torch on both backends.
+# Paged cache (the same kernel template once more): with block_tables [B, MB] the cache is a
+# block pool [2, NB, KVH, BS, D] shared by the sequences; positions stay logical, L = MB*BS. The
+# 'ref' kernel gathers, runs the contiguous oracle and scatters the appended rows back.
 # =============================================================================
 def _rotate_rows(x, cos, sin, dims):
     """Half-split rotation inside each of ``dims`` chunks: x [B, H, D] fp32, cos/sin [B, D]."""
@@ -972,7 +975,9 @@ def _mmha_ref(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0, qu
 
 
 @R.register_kernel('mmha_decode', 'hip', dtypes=_FLOATS)
-def _mmha_hip(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0, quant=None):
+def _mmha_hip(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0, quant=None, tables=None):
+    """``tables`` (device int32 [B, MB]) makes ``cache`` the block pool [2, NB, KVH, BS, D] and
+    the logical capacity L = MB*BS; the pool and the table were validated by the caller."""
     if qkv.dim() == 3:              # [B, H + 2*KVH, D]; the 4-D form is the same memory with KVH = H
         B, D, KVH = qkv.shape[0], qkv.shape[2], cache.shape[2]
         H = qkv.shape[1] - 2 * KVH
@@ -982,7 +987,7 @@ def _mmha_hip(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0, qu
     else:
         B, _, H, D = qkv.shape
         KVH = H
-    L = cache.shape[3]
+    L = cache.shape[3] if tables is None else tables.shape[1] * cache.shape[3]
     t_dev = None
     if isinstance(t, torch.Tensor):  # device position (HIP-graph decode loops): read in-kernel
         if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
@@ -992,7 +997,8 @@ def _mmha_hip(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0, qu
     cache_ok = cache.dtype == qkv.dtype if quant is None else \
         (cache.dtype == torch.uint8 and cache.is_cuda and cache.data_ptr() % 8 == 0)
     if not (qkv.is_contiguous() and cache.is_contiguous() and cache_ok and
-            tuple(cache.shape) == (2, B, KVH, L, D) and D in (64, 128, 256) and
+            (tuple(cache.shape) == (2, B, KVH, L, D) if tables is None else
+             tuple(cache.shape[2:]) == (KVH, cache.shape[3], D)) and D in (64, 128, 256) and
             (t_dev is not None or 0 <= t < L)):
         raise ValueError(f"mmha_decode: qkv {tuple(qkv.shape)} / cache {tuple(cache.shape)} / "
                          f"t={t} not supported by the HIP kernel")
@@ -1031,6 +1037,17 @@ def _mmha_hip(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0, qu
     else:
         # a float cache: the model dtype's code, no scales (the quantisation arguments unused)
         cache_dt, scales_ptr, bstride, round_type, qmax, qmin = _dt(qkv), 0, 0, 1, 127.0, -127.0
+    if tables is not None:
+        _native.lib().mmha_decode_paged(_ptr(qkv), _ptr(cache), _ptr(mask) if mask is not None else 0,
+                                        _ptr(ws), _ptr(out), B, H, KVH, cache.shape[1], cache.shape[3],
+                                        tables.shape[1], D, int(t),
+                                        _ptr(t_dev) if t_dev is not None else 0, splits, mlen,
+                                        1.0 / math.sqrt(D), _dt(qkv),
+                                        _ptr(seq_lens) if seq_lens is not None else 0,
+                                        _ptr(rotary) if rotary is not None else 0, int(rotary_dims),
+                                        _stream(), cache_dt, scales_ptr, bstride, round_type, qmax, qmin,
+                                        _ptr(tables))
+        return out
     _native.lib().mmha_decode(_ptr(qkv), _ptr(cache), _ptr(mask) if mask is not None else 0,
                               _ptr(ws), _ptr(out), B, H, KVH, L, D, int(t),
                               _ptr(t_dev) if t_dev is not None else 0, splits, mlen,
@@ -1039,6 +1056,101 @@ def _mmha_hip(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0, qu
                               _ptr(rotary) if rotary is not None else 0, int(rotary_dims), _stream(),
                               cache_dt, scales_ptr, bstride, round_type, qmax, qmin)
     return out
+
+
+# --- paged cache: a block pool [2, NB, KVH, BS, D] and per-sequence block tables [B, MB] ------
+def _gather_pool(pool, tables):
+    """The contiguous cache [2, B, KVH, MB*BS, D] that ``tables`` (long [B, MB]) describes, and
+    which entries name a block of the pool. A block with a bad entry reads as zeros (byte 128
+    for a uint8 pool): its positions are masked, and a masked NaN would still poison a sum."""
+    _, NB, KVH, BS, D = pool.shape
+    B, MB = tables.shape
+    ok = (tables >= 0) & (tables < NB)
+    g = pool[:, tables.clamp(0, NB - 1)]                          # [2, B, MB, KVH, BS, D]
+    fill = 128 if pool.dtype == torch.uint8 else 0
+    g = torch.where(ok[None, :, :, None, None, None], g, torch.full_like(g[:1, :1, :1, :1, :1, :1], fill))
+    return g.permute(0, 1, 3, 2, 4, 5).reshape(2, B, KVH, MB * BS, D).contiguous(), ok
+
+
+@R.register_kernel('mmha_decode_paged', 'ref')
+def _mmha_paged_ref(qkv, pool, t, mask, tables, seq_lens=None, rotary=None, rotary_dims=0, quant=None):
+    """Paging around the contiguous oracle, for any block size: gather every sequence's blocks,
+    mask what a bad entry covers, guard a sequence whose own block is bad, run ``_mmha_ref`` and
+    scatter the appended rows back into the pool."""
+    BS = pool.shape[3]
+    B, MB = tables.shape
+    L = MB * BS
+    tab = tables.to(device=pool.device, dtype=torch.long)
+    cache, ok = _gather_pool(pool, tab)
+    tt = int(t.reshape(-1)[0]) if isinstance(t, torch.Tensor) else int(t)
+    lens = [tt] * B if seq_lens is None else [int(x) for x in seq_lens.reshape(-1).tolist()]
+    own_ok = [0 <= n < L and bool(ok[b, n // BS]) for b, n in enumerate(lens)]
+    if not bool(ok.all()):
+        bad = (~ok).repeat_interleave(BS, 1)                      # [B, L] positions without a block
+        mlen = L if mask is None else mask.reshape(B, -1).shape[1]
+        m = torch.zeros(B, mlen, device=qkv.device) if mask is None else mask.reshape(B, -1).float().clone()
+        n = min(mlen, L)
+        m[:, :n] = m[:, :n].masked_fill(bad[:, :n].to(m.device), float('-inf'))
+        mask = m
+        if not all(own_ok[b] or not 0 <= n < L for b, n in enumerate(lens)):
+            # an own block that is bad: position L is out of range for the oracle's guard
+            seq_lens = torch.tensor([n if own_ok[b] else L for b, n in enumerate(lens)],
+                                    dtype=torch.int32, device=qkv.device)
+    out = _mmha_ref(qkv, cache, t, mask, seq_lens=seq_lens, rotary=rotary, rotary_dims=rotary_dims,
+                    quant=quant)
+    for b, n in enumerate(lens):                                  # a guarded row comes back as it was
+        if own_ok[b]:
+            pool[:, tab[b, n // BS], :, n % BS] = cache[:, b, :, n]
+    return out
+
+
+@R.register_kernel('mmha_decode_paged', 'hip', dtypes=_FLOATS)
+def _mmha_paged_hip(qkv, pool, t, mask, tables, seq_lens=None, rotary=None, rotary_dims=0, quant=None):
+    BS = pool.shape[3]
+    if BS < 16 or BS & (BS - 1):
+        raise ValueError(f"mmha_decode: block size {BS} is not supported by the HIP kernel (a power "
+                         "of two >= 16)")
+    if not (tables.is_cuda and tables.dtype == torch.int32 and tables.is_contiguous() and
+            tables.dim() == 2 and tables.shape[0] == qkv.shape[0]):
+        raise ValueError(f"mmha_decode: block_tables must be a contiguous CUDA int32 "
+                         f"[{qkv.shape[0]}, MB] tensor")
+    return _mmha_hip(qkv, pool, t, mask, seq_lens=seq_lens, rotary=rotary, rotary_dims=rotary_dims,
+                     quant=quant, tables=tables)
+
+
+def _block_tables_arg(qkv, pool, tables, time_step, seq_lens):
+    """Validate ``block_tables`` against the pool and, when the table, ``seq_lens`` and
+    ``time_step`` are all host values, what it says about this step. Returns the table as an
+    int32 tensor on qkv's device (a device table is passed through, never synced)."""
+    B = qkv.shape[0]
+    if pool.dim() != 5 or pool.shape[0] != 2:
+        raise ValueError(f"mmha_decode: with block_tables the cache is the block pool "
+                         f"[2, NB, KVH, BS, D], got {tuple(pool.shape)}")
+    NB, BS = pool.shape[1], pool.shape[3]
+    on_host = not (isinstance(tables, torch.Tensor) and tables.is_cuda)
+    tab = torch.as_tensor(tables)
+    if tab.dim() != 2 or tab.shape[0] != B or tab.shape[1] < 1 or tab.dtype.is_floating_point:
+        raise ValueError(f"mmha_decode: block_tables must be an integer [{B}, MB] table, got "
+                         f"{tuple(tab.shape)} {tab.dtype}")
+    lens_host = seq_lens is None or not (isinstance(seq_lens, torch.Tensor) and seq_lens.is_cuda)
+    if on_host and lens_host and not isinstance(time_step, torch.Tensor):
+        L = tab.shape[1] * BS
+        lens = [int(time_step)] * B if seq_lens is None else \
+            [int(n) for n in torch.as_tensor(seq_lens).reshape(-1).tolist()]
+        rows = tab.tolist()
+        appended = []
+        for b, n in enumerate(lens[:B]):
+            if not 0 <= n < L:
+                continue                                          # the position checks name this one
+            bad = [e for e in rows[b][:n // BS + 1] if not 0 <= e < NB]
+            if bad:
+                raise ValueError(f"mmha_decode: block_tables[{b}] covers positions [0, {n}] with "
+                                 f"entry {bad[0]}, outside the pool's [0, {NB})")
+            appended.append(rows[b][n // BS])
+        if len(set(appended)) != len(appended):
+            raise ValueError(f"mmha_decode: two sequences append to the same block "
+                             f"(blocks {appended}); only blocks that are read may be shared")
+    return tab.to(device=qkv.device, dtype=torch.int32).contiguous()
 
 
 _CACHE_U8 = 3            # cache dtype code of the uint8 KV cache (decode_attn.hip kCacheU8)
@@ -1057,7 +1169,7 @@ def rotary_in_kernel(head_dim, rotary_dims):
 def mmha_decode(qkv, cache, time_step, mask=None, seq_lens=None, rotary=None, rotary_dims=0,
                 cache_k_quant_scales=None, cache_v_quant_scales=None, cache_k_dequant_scales=None,
                 cache_v_dequant_scales=None, quant_round_type=1, quant_max_bound=127.0,
-                quant_min_bound=-127.0):
+                quant_min_bound=-127.0, block_tables=None):
     """One decode step of multi-head attention; returns [B, H, D] and appends K/V to
     ``cache`` at ``time_step`` in place. ``time_step`` may be a CUDA int32 tensor: the kernel
     reads it on the device (no host sync), so the step can live in a captured HIP graph.
@@ -1084,9 +1196,26 @@ def mmha_decode(qkv, cache, time_step, mask=None, seq_lens=None, rotary=None, ro
     scales are not synced. ``quant_round_type`` 1 rounds half away from zero, 0 half to even.
     The new token's k (rotated first, not rounded to the model dtype) and v are quantised from
     fp32, written at ``t_b`` and attended to as those levels, so a later step that reads the
-    row back agrees with this one. Everything else behaves as for a float cache."""
+    row back agrees with this one. Everything else behaves as for a float cache.
+
+    Paged cache: with ``block_tables`` ([B, MB] integers; list, numpy array or tensor) ``cache``
+    is a block pool [2, NB, KVH, BS, D] (the K plane, then the V plane; float or ``uint8``) that
+    sequences share: entry ``j`` of row ``b`` is the physical block holding logical positions
+    [j*BS, (j+1)*BS) of sequence ``b``, ``-1`` for none. Positions stay logical everywhere
+    (``time_step``, ``seq_lens``, the mask) with capacity ``L = MB*BS``, and quantisation scales
+    stay per sequence, not per block. Sequences may share blocks they only read (a common
+    prefix). A host table with host positions is validated: every block covering [0, t_b] is in
+    [0, NB) and no two sequences append to the same block. A device table is not synced and not
+    trusted: an entry outside [0, NB) is never addressed, its keys carry weight 0, and a
+    sequence whose own position lies in such a block gets zeros and no write. On the GPU ``BS``
+    must be a power of two >= 16."""
     if not isinstance(time_step, torch.Tensor):
         time_step = int(time_step)
+    if block_tables is not None:
+        return _mmha_decode_paged(qkv, cache, time_step, mask, seq_lens, rotary, rotary_dims,
+                                  block_tables, cache_k_quant_scales, cache_v_quant_scales,
+                                  cache_k_dequant_scales, cache_v_dequant_scales, quant_round_type,
+                                  quant_max_bound, quant_min_bound)
     quant = _kv_quant_args(qkv.shape[0], cache, cache_k_quant_scales, cache_v_quant_scales,
                            cache_k_dequant_scales, cache_v_dequant_scales, quant_round_type,
                            quant_max_bound, quant_min_bound, qkv.device)
@@ -1125,6 +1254,51 @@ def mmha_decode(qkv, cache, time_step, mask=None, seq_lens=None, rotary=None, ro
         rotary = rotary.reshape(2, B, D).to(device=qkv.device, dtype=torch.float32).contiguous()
     return R.dispatch('mmha_decode', qkv, qkv.contiguous(), cache, time_step, mask,
                       seq_lens=seq_lens, rotary=rotary, rotary_dims=int(rotary_dims), **qkw)
+
+
+def _mmha_decode_paged(qkv, pool, time_step, mask, seq_lens, rotary, rotary_dims, block_tables, k_quant,
+                       v_quant, k_dequant, v_dequant, round_type, qmax, qmin):
+    """``mmha_decode`` with ``block_tables``: the argument checks of the contiguous form with
+    the pool in the cache's place and L = MB*BS, then the paged kernel."""
+    B, D = qkv.shape[0], qkv.shape[-1]
+    tables = _block_tables_arg(qkv, pool, block_tables, time_step, seq_lens)
+    L = tables.shape[1] * pool.shape[3]
+    quant = _kv_quant_args(B, pool, k_quant, v_quant, k_dequant, v_dequant, round_type, qmax, qmin,
+                           qkv.device)
+    if pool.shape[4] != D:
+        raise ValueError(f"mmha_decode: pool {tuple(pool.shape)} does not fit qkv {tuple(qkv.shape)}")
+    KVH = pool.shape[2]
+    if qkv.dim() == 3:
+        H = qkv.shape[1] - 2 * KVH
+        if H <= 0 or H % KVH != 0:
+            raise ValueError(f"mmha_decode: qkv has {qkv.shape[1]} head rows and the pool {KVH} "
+                             f"K/V heads; {qkv.shape[1]} - 2*{KVH} query heads must be a "
+                             f"positive multiple of {KVH}")
+        if H == KVH:
+            qkv = qkv.reshape(B, 3, H, D)
+    elif qkv.shape[2] != KVH:
+        raise ValueError(f"mmha_decode: pool {tuple(pool.shape)} does not fit qkv {tuple(qkv.shape)}")
+    if seq_lens is not None:
+        on_host = not (isinstance(seq_lens, torch.Tensor) and seq_lens.is_cuda)
+        seq_lens = torch.as_tensor(seq_lens).reshape(-1)
+        if seq_lens.numel() != B:
+            raise ValueError(f"mmha_decode: seq_lens has {seq_lens.numel()} entries for batch {B}")
+        if on_host and not isinstance(time_step, torch.Tensor):
+            if not all(0 <= int(n) <= time_step < L for n in seq_lens.tolist()):
+                raise ValueError(f"mmha_decode: need 0 <= seq_lens <= time_step < {L}, got "
+                                 f"seq_lens={seq_lens.tolist()} time_step={time_step}")
+        seq_lens = seq_lens.to(device=qkv.device, dtype=torch.int32).contiguous()
+    if rotary is not None:
+        if isinstance(rotary, (tuple, list)):
+            rotary = torch.stack([torch.as_tensor(r).reshape(B, D) for r in rotary])
+        if int(rotary_dims) < 1:
+            raise ValueError("mmha_decode: rotary needs rotary_dims >= 1")
+        rotary = rotary.reshape(2, B, D).to(device=qkv.device, dtype=torch.float32).contiguous()
+    if not isinstance(time_step, torch.Tensor) and not 0 <= time_step < L:
+        raise ValueError(f"mmha_decode: time_step {time_step} outside the table's [0, {L})")
+    return R.dispatch('mmha_decode_paged', qkv, qkv.contiguous(), pool, time_step, mask, tables,
+                      seq_lens=seq_lens, rotary=rotary, rotary_dims=int(rotary_dims),
+                      **({} if quant is None else {'quant': quant}))
 
 
 # =============================================================================

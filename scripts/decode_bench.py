@@ -2,9 +2,10 @@
 the same KV cache, a ragged batch (per-sequence seq_lens) next to its padded-and-masked twin,
 grouped-query attention next to the expanded multi-head cache and the byte floor, end-to-end
 FusedMultiTransformer decode steps/s, and the 8-bit KV cache next to the bf16 one (kernel rows
-and the graph decoder).
+and the graph decoder), and the paged cache (a block pool behind shuffled block tables) next to
+the contiguous cache of the same logical contents.
 
-usage: python scripts/decode_bench.py [--quick]"""
+usage: python scripts/decode_bench.py [--quick] [--sections plain,ragged,gqa,e2e,q8,paged]"""
 import argparse
 import json
 import math
@@ -48,8 +49,26 @@ def bench_graph(fn, calls=20, reps=10):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--quick', action='store_true')
+    ap.add_argument('--sections', default='plain,ragged,gqa,e2e,q8,paged',
+                    help='comma-separated: plain, ragged, gqa, e2e, q8, paged')
     a = ap.parse_args()
+    sections = set(a.sections.split(','))
     from paddle_ray_amd.ops import fused as K
+    if 'plain' in sections:
+        plain_rows(a, K)
+    if 'ragged' in sections:
+        ragged_rows(K)
+    if 'gqa' in sections:
+        gqa_rows(K)
+    if 'e2e' in sections:
+        end_to_end(a)
+    if 'q8' in sections:
+        q8_rows(K)
+    if 'paged' in sections:
+        paged_rows(K)
+
+
+def plain_rows(a, K):
     rows = []
     shapes = [(1, 32, 128, 4095), (8, 32, 128, 4095), (32, 16, 128, 2047), (64, 32, 128, 1023),
               (8, 16, 64, 8191)]
@@ -72,6 +91,9 @@ def main():
                          sdpa_us=round(ref * 1e6, 1), hip_TBps=round(gb / hip / 1e3, 2),
                          sdpa_TBps=round(gb / ref / 1e3, 2), splits=K._native.lib().mmha_splits(B, H, t)))
         print(json.dumps(rows[-1]), flush=True)
+
+
+def ragged_rows(K):
     # ragged batch: every sequence at its own length (seq_lens), next to the same batch run
     # the only way possible without it — all sequences at 4095 behind an additive mask.
     # TB/s counts the bytes actually valid, sum(len_b + 1) K and V rows, for both.
@@ -90,6 +112,9 @@ def main():
                           masked_us=round(masked * 1e6, 1), valid_GB=round(gb, 4),
                           ragged_TBps=round(gb / ragged / 1e3, 2),
                           masked_TBps=round(gb / masked / 1e3, 2))), flush=True)
+
+
+def gqa_rows(K):
     # grouped-query attention (KVH K/V heads shared by H query heads): the GQA kernel on the
     # KVH-head cache, next to the plain kernel on the cache expanded to H heads (the only way
     # to run such a model without it) and the plain kernel at H = KVH (the same cache bytes with
@@ -112,6 +137,9 @@ def main():
                               same_bytes_us=round(same * 1e6, 1), kv_GB=round(gb, 4),
                               gqa_TBps=round(gb / gqa / 1e3, 2),
                               splits=K._native.lib().mmha_splits(B, KVH, t))), flush=True)
+
+
+def end_to_end(a):
     # end-to-end decode: 24-layer 2048-wide model (GPT-3 1.3B shape), batch 8
     import paddle_ray_amd as paddle
     from paddle_ray_amd.incubate.nn import FusedMultiTransformer
@@ -160,6 +188,9 @@ def main():
                           bf16_cache_ms_per_token_step=round(dg * 1e3, 3),
                           tokens_per_s=round(B / d8, 1), cache_MiB_per_sequence_bf16=round(mib16, 1),
                           cache_MiB_per_sequence_int8=round(mib8, 1))), flush=True)
+
+
+def q8_rows(K):
     # 8-bit KV cache (uint8 + per-head scales) next to the bf16 cache on the same problem: the
     # plain shapes at batch 1 and 8, then the two grouped-query shapes. TB/s counts the cache
     # bytes each kernel streams: 1 byte per element for int8, 2 for bf16. The *_graph_us columns
@@ -190,6 +221,50 @@ def main():
                               bf16_graph_TBps=round(2 * elems / bfg / 1e12, 2),
                               int8_over_bf16_graph=round(q8g / bfg, 3))), flush=True)
         del cache16, cache8
+
+
+def paged_rows(K):
+    # paged cache: the same logical contents cut into blocks of a pool in shuffled physical
+    # order (sequences interleaved) behind a device block table, next to the contiguous cache,
+    # both replayed from a captured HIP graph as the decoder runner does. paged_over_contig is
+    # the price of the table lookup; TB/s counts the cache bytes either kernel streams.
+    D, t, Bq = 128, 4095, 8
+    L = t + 1
+    for H, KVH, BS, u8 in ((32, 32, 16, False), (32, 32, 64, False), (32, 32, 128, False),
+                           (32, 8, 64, False), (32, 32, 64, True), (32, 8, 64, True)):
+        row = torch.randn(Bq, H + 2 * KVH, D, device='cuda', dtype=torch.bfloat16)
+        if H == KVH:
+            row = row.reshape(Bq, 3, H, D)
+        cache = torch.randn(2, Bq, KVH, L, D, device='cuda', dtype=torch.bfloat16)
+        kw = {}
+        if u8:
+            packed = torch.empty(4, 1, KVH, device='cuda')
+            packed[:2] = 127.0 / 4.5
+            packed[2:] = 4.5 / 127.0
+            cache = torch.stack([K.kv_quantize(cache[i], packed[i, 0]) for i in range(2)])
+            kw = dict(cache_k_quant_scales=packed[0, 0], cache_v_quant_scales=packed[1, 0],
+                      cache_k_dequant_scales=packed[2, 0], cache_v_dequant_scales=packed[3, 0])
+        MB = L // BS
+        perm = torch.randperm(Bq * MB, generator=torch.Generator().manual_seed(BS))
+        table = perm.reshape(MB, Bq).t().contiguous().to(device='cuda', dtype=torch.int32)
+        pool = torch.empty(2, Bq * MB, KVH, BS, D, device='cuda', dtype=cache.dtype)
+        pool[:, table.long()] = cache.reshape(2, Bq, KVH, MB, BS, D).permute(0, 1, 3, 2, 4, 5)
+        with torch.no_grad():
+            same = bool(torch.equal(K.mmha_decode(row, cache, t, **kw),
+                                    K.mmha_decode(row, pool, t, block_tables=table, **kw)))
+            cg = bench_graph(lambda: K.mmha_decode(row, cache, t, **kw))
+            pg = bench_graph(lambda: K.mmha_decode(row, pool, t, block_tables=table, **kw))
+        ce = bench(lambda: K.mmha_decode(row, cache, t, **kw))
+        pe = bench(lambda: K.mmha_decode(row, pool, t, block_tables=table, **kw))
+        nbytes = 2 * Bq * KVH * L * D * cache.element_size()
+        print(json.dumps(dict(paged=True, B=Bq, H=H, KVH=KVH, D=D, ctx=L, block_size=BS,
+                              cache='uint8' if u8 else 'bf16', contig_graph_us=round(cg * 1e6, 1),
+                              paged_graph_us=round(pg * 1e6, 1), paged_over_contig=round(pg / cg, 3),
+                              contig_us=round(ce * 1e6, 1), paged_us=round(pe * 1e6, 1),
+                              contig_graph_TBps=round(nbytes / cg / 1e12, 2),
+                              paged_graph_TBps=round(nbytes / pg / 1e12, 2), bit_equal=same)), flush=True)
+        del cache, pool
+
 
 if __name__ == '__main__':
     main()
