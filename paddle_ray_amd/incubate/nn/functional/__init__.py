@@ -255,6 +255,12 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
       ``time_step`` stays the phase switch and the batch-wide upper bound (max of seq_lens).
       ``rotary_embs`` ([2, B, 1, 1, D], each sequence's own position) is applied inside the
       kernel when the head dim allows it, else by the torch rotation before it.
+      With x [B, S, E], S > 1, the step takes S new tokens per sequence and equals S
+      consecutive one-token steps (``ops.fused.mmha_decode_multi``): token j of sequence b is
+      appended at ``seq_lens[b] + j`` (``time_step + j`` without ``seq_lens``) and attends to
+      everything up to itself; ``rotary_embs`` is then [2, B, 1, S, D], row j for that position,
+      and a mask row is shared by the S tokens. A sequence without room for all S tokens gets
+      zero attention rows and no write.
     * grouped-query attention (``gqa_group_size`` = KVH > 0, the number of K/V heads): qkv
       weights are [H + 2*KVH, D, E] ([E, H + 2*KVH, D] with ``trans_qkvw=False``), biases
       [H + 2*KVH, D] — the query heads, then the k heads, then the v heads — and
@@ -297,13 +303,11 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
             else int(ts.reshape(-1)[0])
     else:
         t = int(time_step) if decode else None
-    if decode and S != 1:
-        raise ValueError("fused_multi_transformer: decode phase (time_step given) takes one token")
     rot = krot = None
     if rotary_embs is not None and rotary_emb_dims:
         re = _u(rotary_embs)                          # [2, B, 1, S, D]
         if decode and K.rotary_in_kernel(re.shape[-1], rotary_emb_dims):
-            krot = re.reshape(2, B, -1)               # rotated inside the decode kernel
+            krot = re.reshape(2, B, -1) if S == 1 else re.reshape(2, B, S, -1)   # rotated inside the decode kernel
         else:
             rot = (re[0].reshape(B, S, -1), re[1].reshape(B, S, -1))
     mask = _t(attn_mask)
@@ -358,10 +362,16 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
         if decode:
             if cache is None:
                 raise ValueError("fused_multi_transformer: time_step needs cache_kvs")
-            o = K.mmha_decode(qkv[:, 0].contiguous(), cache, t, mask, seq_lens=sl, rotary=krot,
-                              rotary_dims=rotary_emb_dims if krot is not None else 0,
-                              **({} if block_tables is None else {'block_tables': _t(block_tables)}),
-                              **qkw).reshape(B, 1, H * D)
+            if S == 1:
+                o = K.mmha_decode(qkv[:, 0].contiguous(), cache, t, mask, seq_lens=sl, rotary=krot,
+                                  rotary_dims=rotary_emb_dims if krot is not None else 0,
+                                  **({} if block_tables is None else {'block_tables': _t(block_tables)}),
+                                  **qkw).reshape(B, 1, H * D)
+            else:                                    # S tokens per sequence in one pass over the cache
+                o = K.mmha_decode_multi(qkv.reshape(B, S, -1, D), cache, t, mask, seq_lens=sl, rotary=krot,
+                                        rotary_dims=rotary_emb_dims if krot is not None else 0,
+                                        **({} if block_tables is None else {'block_tables': _t(block_tables)}),
+                                        **qkw).reshape(B, S, H * D)
         else:
             if KVH:
                 q, k, v = qkv[:, :, :H], qkv[:, :, H:H + KVH], qkv[:, :, H + KVH:]

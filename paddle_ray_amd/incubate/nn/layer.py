@@ -272,6 +272,27 @@ class FusedMultiTransformerDecoder:
     through table row ``b`` and sets the slot's position to ``S`` (and, with dynamic int8
     scales, the slot's scales from its prompt), leaving the other slots and the graph alone.
     On the GPU ``BS`` must be a power of two >= 16.
+
+    Several tokens per step: ``step_multi(x)`` (x [B, T, E]) scores T new tokens per slot at the
+    slots' current positions in one pass over the caches, equal to T ``step`` calls, writes
+    their K/V and advances nothing; ``commit(accepted)`` then advances every slot by its own
+    count in [0, T]. Rows written past the new position are dead: the next step overwrites them
+    (paged: blocks already allocated stay with the slot). It always runs the per-sequence graph
+    (a runner in uniform mode switches to it), one captured graph per T, and mixes freely with
+    ``step``. Speculative decoding with a draft model proposing T - 1 tokens after the last
+    accepted one:
+
+        x = embed(last)                              # [B, 1, E]
+        while not done:
+            draft = propose(last, T - 1)             # [B, T - 1] token ids from the draft model
+            toks = cat([last, draft], 1)             # [B, T]
+            h = dec.step_multi(embed(toks))          # [B, T, E]: row j scores the token after toks[:, j]
+            pred = head(h).argmax(-1)                # [B, T]
+            ok = (pred[:, :-1] == draft).int().cumprod(1).sum(1)   # drafts accepted per slot
+            dec.commit(ok + 1)                       # toks[:, :ok + 1] are now part of the sequence
+            last = pred.gather(1, ok[:, None])       # the model's own next token
+    On the GPU T times the query heads per K/V head (T rounded up to a power of two) must not
+    exceed 8 (``ops.fused.MULTI_MAX_ROWS``).
     """
 
     def __init__(self, model, batch_size, max_seq_len, use_graph=True, kv_cache_dtype=None,
@@ -344,6 +365,8 @@ class FusedMultiTransformerDecoder:
         self.use_graph = use_graph and self.dev.type == 'cuda'
         self._graph = None
         self._out = None
+        self._multi = {}              # T -> [x buffer [B, T, E], captured graph, its output]
+        self._last_T = None           # T of the step_multi that commit() may follow
 
     def _caches(self):
         from ...framework.core import Tensor
@@ -364,6 +387,7 @@ class FusedMultiTransformerDecoder:
         self.rot = tab.to(device=self.dev, dtype=torch.float32).contiguous()
         self.rot_dims = int(rotary_emb_dims)
         self._graph = None
+        self._multi = {}
 
     def prefill(self, x, attn_mask=None, seq_lens=None):
         """Context phase over the prompt (caches filled in place); decode continues at S0, or
@@ -455,6 +479,23 @@ class FusedMultiTransformerDecoder:
             e = self._free.pop()
             self.tables[b, len(self._blocks[b])].fill_(e)
             self._blocks[b].append(e)
+
+    def _grow_multi(self, T):
+        """Before a multi-token step: every live slot gets the blocks that cover [p, p + T).
+        Raises before it changes anything when the free list is too short."""
+        cap = self.MB * self.BS
+        want = [(b, (min(p + T, cap) - 1) // self.BS + 1 - len(self._blocks[b]))
+                for b, p in enumerate(self._pos) if p is not None and p < self.L]
+        want = [(b, k) for b, k in want if k > 0]
+        if sum(k for _, k in want) > len(self._free):
+            raise RuntimeError(f"FusedMultiTransformerDecoder: {T} tokens per slot need "
+                               f"{sum(k for _, k in want)} new blocks and {len(self._free)} are free; "
+                               "release a slot or use a larger pool")
+        for b, k in want:
+            for _ in range(k):
+                e = self._free.pop()
+                self.tables[b, len(self._blocks[b])].fill_(e)
+                self._blocks[b].append(e)
 
     def release(self, b):
         """Slot ``b`` leaves the batch: its blocks go back to the free list, its table row to -1
@@ -556,6 +597,86 @@ class FusedMultiTransformerDecoder:
         out, _ = self.model(Tensor(self.x_buf), attn_mask=Tensor(self.mask), caches=self._caches(),
                             time_step=Tensor(self.t), **kw)
         return out._t
+
+    def _step_multi_eager(self, T):
+        import torch
+        from ...framework.core import Tensor
+        kw = dict(self._qkw)
+        kw['seq_lens'] = Tensor(self.lens)
+        if self.paged:
+            kw['block_tables'] = Tensor(self.tables)
+        if self.rot is not None:
+            # token j of a slot: the row of its position + j (a parked or full slot is guarded:
+            # any row will do)
+            pos = (self.lens[:, None] + torch.arange(T, device=self.dev, dtype=torch.int32)[None, :]
+                   ).clamp(max=self.L - 1)
+            r = self.rot.index_select(1, pos.reshape(-1)).view(2, self.B, 1, T, -1)
+            kw.update(rotary_embs=Tensor(r), rotary_emb_dims=self.rot_dims)
+        out, _ = self.model(Tensor(self._multi[T][0]), attn_mask=Tensor(self.mask), caches=self._caches(),
+                            time_step=Tensor(self.t), **kw)
+        return out._t
+
+    def step_multi(self, x):
+        """T tokens for every sequence (x [B, T, E]) at the slots' current positions, in one pass
+        over the caches: returns [B, T, E], row j what the j-th of T ``step`` calls would return.
+        The K/V of all T tokens are written; no position advances until ``commit``."""
+        import torch
+        from ...framework.core import Tensor
+        xt = x._t if hasattr(x, '_t') else x
+        if xt.dim() != 3 or xt.shape[0] != self.B or xt.shape[1] < 1:
+            raise ValueError(f"FusedMultiTransformerDecoder.step_multi: x must be [{self.B}, T, E] with "
+                             f"T >= 1, got {tuple(xt.shape)}")
+        T = int(xt.shape[1])
+        if self.paged:                # blocks first: an exhausted pool raises with nothing changed
+            self._grow_multi(T)
+        if not self.ragged:           # every slot continues from the common position, on its own
+            self.lens.copy_(self.t.expand(self.B))
+            self.ragged, self._graph = True, None
+        if T not in self._multi:
+            self._multi[T] = [torch.zeros(self.B, T, xt.shape[2], device=self.dev, dtype=self.dtype),
+                              None, None]
+        ent = self._multi[T]
+        ent[0].copy_(xt)
+        self._last_T = T
+        with torch.no_grad():
+            if not self.use_graph:
+                return Tensor(self._step_multi_eager(T))
+            if ent[1] is None:
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):  # warm-up (writes the same T cache rows, nothing advances)
+                    self._step_multi_eager(T)
+                torch.cuda.current_stream().wait_stream(s)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    ent[2] = self._step_multi_eager(T)
+                ent[1] = g
+            ent[1].replay()
+        return Tensor(ent[2].clone())
+
+    def commit(self, accepted):
+        """After ``step_multi``: slot ``b`` keeps the first ``accepted[b]`` (in [0, T]) of its T
+        tokens and continues behind them. ``accepted`` is a list, array or tensor of B counts (a
+        tensor costs one sync, for the host mirror of the positions)."""
+        import torch
+        if self._last_T is None:
+            raise RuntimeError("FusedMultiTransformerDecoder.commit follows a step_multi")
+        a = accepted._t if hasattr(accepted, '_t') else accepted
+        host = [int(n) for n in (a.reshape(-1).tolist() if isinstance(a, torch.Tensor)
+                                 else torch.as_tensor(a).reshape(-1).tolist())]
+        if len(host) != self.B or not all(0 <= n <= self._last_T for n in host):
+            raise ValueError(f"FusedMultiTransformerDecoder.commit: need {self.B} counts in "
+                             f"[0, {self._last_T}], got {host}")
+        if self.paged:                # a released slot stays parked
+            host = [0 if p is None else n for n, p in zip(host, self._pos)]
+            self._pos = [p if p is None else p + n for n, p in zip(host, self._pos)]
+            live = [p for p in self._pos if p is not None]
+            self.lens.add_(torch.tensor(host, dtype=torch.int32).to(self.dev))
+            self.t.fill_(max(live) if live else 0)
+        else:
+            self.lens.add_(torch.tensor(host, dtype=torch.int32).to(self.dev))
+            self.t.copy_(self.lens.max().reshape(1))
+        self._last_T = None
 
     def _advance(self):
         self.t.add_(1)

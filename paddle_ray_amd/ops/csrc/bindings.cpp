@@ -109,6 +109,10 @@ PYBIND11_MODULE(_pra_hip, m) {
   Launch<&pra_mmha_decode_paged>::def(m, "mmha_decode_paged",
                                       "block size not a power of two >= 16, null block table, or anything "
                                       "mmha_decode refuses at L = MB*BS");
+  // n_tok tokens per sequence in one cache pass; a null block table means the contiguous cache
+  Launch<&pra_mmha_decode_multi>::def(m, "mmha_decode_multi",
+                                      "n_tok < 1, more than 8 query rows per K/V row, or anything mmha_decode / "
+                                      "mmha_decode_paged refuses");
   Launch<&pra_bias_gelu_fwd>::def(m, "bias_gelu_fwd");
   Launch<&pra_bias_gelu_bwd>::def(m, "bias_gelu_bwd");
   Launch<&pra_bias_gelu_bwd_db>::def(m, "bias_gelu_bwd_db");

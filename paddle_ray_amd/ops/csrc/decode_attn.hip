@@ -66,6 +66,21 @@
 //    16-byte row loads depend on a 4-byte table load, so the entries of the next iteration's
 //    keys are fetched one iteration ahead, after this iteration's row loads are issued and
 //    before its math: as many row bytes stay in flight per lane as without paging.
+//  * several new tokens per sequence (MULTI instantiations, always EXT; a single-token one is
+//    compiled without any of it): n_tok tokens at positions [t_b, t_b + n_tok), equal to n_tok
+//    consecutive single-token steps. A K/V head then has NQ = R * Tp query rows (Tp = n_tok
+//    rounded up to a power of two, NQ in {2, 4, 8}; row i is token i / R, query head i % R), which
+//    are the register states of the R = NQ instantiation, so the template's R counts rows and the
+//    ratio is a run-time shift. The loop streams only what the cache held, [lo, min(hi, t_b)):
+//    every row sees all of it, so it has no per-row test and no new-token registers. The
+//    workgroup whose key range holds t_b then runs a tail before the merges: lane group j takes
+//    token j's k / v from the qkv buffer, rotates k with token j's cos / sin, rounds or quantises
+//    it, appends the row at t_b + j and scores it as one more key, with weight 0 for the rows of
+//    earlier tokens (the causal rule among the new tokens). Rows of tokens >= n_tok are zero
+//    queries that are never stored and post no partial. Partials and output are indexed as if
+//    there were n_tok * H heads, so mmha_combine_k runs unchanged on grid (n_tok * H, B). The
+//    guard is all or nothing per sequence; PAGED: n_tok <= 8 < BS, so the new positions lie in at
+//    most two blocks and both entries are checked before anything is addressed.
 #include <type_traits>
 
 #include "common.h"
@@ -174,11 +189,20 @@ __device__ __forceinline__ size_t pool_plane(const PParams<true>& pp, int KVH) {
   return ((size_t)pp.NB * KVH) << pp.shift;
 }
 
-// one kernel parameter for both: empty bases take no room, so a (Q8, false) instantiation is
-// given exactly what it was given before there were pages
-template <bool Q8, bool PAGED> struct XParams : QParams<Q8>, PParams<PAGED> {};
+// what only a MULTI instantiation is given (an empty parameter otherwise)
+template <bool MULTI> struct MParams {};
+template <> struct MParams<true> {
+  int n_tok;   // new tokens per sequence, 2 <= n_tok <= NQ >> rshift
+  int rshift;  // log2 of the query heads per K/V head
+};
 
-template <typename T, int D, int R, bool EXT, bool Q8, bool PAGED>
+// one kernel parameter for all three: empty bases take no room, so a single-token instantiation
+// is given exactly what it was given before there were pages or several tokens
+template <bool Q8, bool PAGED, bool MULTI> struct XParams : QParams<Q8>, PParams<PAGED>, MParams<MULTI> {};
+
+// MULTI: R counts the query rows per K/V head, NQ = (H / KVH) * Tp with Tp = n_tok rounded up to a
+// power of two; the ratio itself is then a run-time value (xp.rshift)
+template <typename T, int D, int R, bool EXT, bool Q8, bool PAGED, bool MULTI = false>
 __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
     const T* __restrict__ qkv,      // [B, H + 2*KVH, D] (bias already added)
     std::conditional_t<Q8, uint8_t, T>* __restrict__ cache,  // [2, B, KVH, L, D]; PAGED: [2, NB, KVH, BS, D]
@@ -190,11 +214,21 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
     float scale,
     const int* __restrict__ seq_lens,  // EXT: [B] per-sequence position, or null
     const float* __restrict__ rot,     // EXT: [2, B, D] cos then sin, or null
-    int rot_dims, XParams<Q8, PAGED> xp) {
+    int rot_dims, XParams<Q8, PAGED, MULTI> xp) {
   static_assert(EXT || !Q8, "the Q8 instantiations are EXT ones");
   static_assert(EXT || !PAGED, "the PAGED instantiations are EXT ones");
+  static_assert(EXT || !MULTI, "the MULTI instantiations are EXT ones");
   [[maybe_unused]] const QParams<Q8>& qp = xp;
   [[maybe_unused]] const PParams<PAGED>& pp = xp;
+  // MULTI: NT new tokens per sequence at positions [t, t + NT); query row i of the R is token
+  // i >> rsh, query head h0 + (i & rmask)
+  [[maybe_unused]] int NT = 1, rsh = 0, rmask = 0;
+  if constexpr (MULTI) {
+    const MParams<MULTI>& mp = xp;
+    NT = mp.n_tok;
+    rsh = mp.rshift;
+    rmask = (1 << rsh) - 1;
+  }
   using C = std::conditional_t<Q8, uint8_t, T>;  // a cache element
   // t_dev (HIP-graph decode loops): the position comes from device memory, so one captured
   // graph serves every step; an out-of-range position writes nothing and outputs zeros
@@ -204,7 +238,7 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
   static_assert(kWaves * KPW >= R, "one lane group per query head in the epilogue");
   const int split = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z;
   const int splits = gridDim.x;
-  const int H = KVH * R, h0 = kvh * R;
+  const int H = MULTI ? KVH << rsh : KVH * R, h0 = MULTI ? kvh << rsh : kvh * R;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int gl = lane % G, grp = lane / G;
   bool in_bound = true;
@@ -215,30 +249,55 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
     }
   }
   bool t_ok = in_bound && t >= 0 && t < L && !(mask && mask_len < t + 1);
+  if constexpr (MULTI) t_ok = in_bound && t >= 0 && t <= L - NT && !(mask && mask_len < t + NT);  // all NT or none
   // PAGED: this sequence's table row, the entry of the token's own block, and in-block mask
   [[maybe_unused]] const int* tab = nullptr;
   [[maybe_unused]] int et = 0, bmask = 0;
+  [[maybe_unused]] int et1 = 0;  // MULTI: the entry of the last new token's block (NT <= 8 < BS: it or the next)
   if constexpr (PAGED) {
     tab = pp.tables + (size_t)b * pp.MB;
     bmask = (1 << pp.shift) - 1;
     if (t_ok) {  // t in [0, L): the column is inside the table row
       et = tab[t >> pp.shift];
       t_ok = (unsigned)et < (unsigned)pp.NB;
+      if constexpr (MULTI) {  // t + NT - 1 < L as well: both entries are checked before any address
+        et1 = tab[(t + NT - 1) >> pp.shift];
+        t_ok = t_ok && (unsigned)et1 < (unsigned)pp.NB;
+      }
     }
   }
   const int lo = split * keys_per_split;
-  const int hi = t_ok ? min(t + 1, lo + keys_per_split) : lo;
+  // MULTI: the loop streams only what the cache held, [lo, min(hi, t)); the workgroup whose key
+  // range holds t then scores and appends the NT new tokens (they never come from the cache)
+  const int hi = t_ok ? min(MULTI ? t : t + 1, lo + keys_per_split) : lo;
+  [[maybe_unused]] bool tail = false;
+  if constexpr (MULTI) tail = t_ok && t >= lo && t < lo + keys_per_split;
 
   const size_t rows = (size_t)H + 2 * KVH;
-  const T* qrow = qkv + ((size_t)b * rows + h0) * D;          // R consecutive query rows
-  const T* knew = qkv + ((size_t)b * rows + H + kvh) * D;
+  const T* qrow = qkv + ((size_t)b * NT * rows + h0) * D;     // R consecutive query rows (MULTI: token 0's)
+  const T* knew = qkv + ((size_t)b * NT * rows + H + kvh) * D;
   const T* vnew = knew + (size_t)KVH * D;
   // PAGED: the two planes; a row index below is then a plane row, not a position
   C* kc = PAGED ? cache : cache + ((size_t)b * KVH + kvh) * (size_t)L * D;
   C* vc = PAGED ? cache + pool_plane(pp, KVH) * D : cache + (((size_t)B + b) * KVH + kvh) * (size_t)L * D;
   const size_t w0 = ((size_t)b * H + h0) * splits + split;    // partial of query head h0; head r: + r*splits
+  // MULTI: output row of query row i, as if there were NT*H heads: (b*NT + token)*H + head
+  [[maybe_unused]] auto orow = [&](int i) { return ((size_t)b * NT + (i >> rsh)) * H + h0 + (i & rmask); };
 
-  if (hi <= lo) {  // a key range past t, or a guarded position: no loads, R empty partials
+  if constexpr (MULTI) {
+    if (hi <= lo && !tail) {  // the same for the NT << rsh rows that exist; the padded ones post nothing
+      const int nrow = NT << rsh;
+      if (splits == 1) {
+        if (wave == 0 && grp == 0) {
+          const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+          for (int i = 0; i < nrow; ++i) store8<T>(out + orow(i) * D + gl * 8, z);
+        }
+      } else if ((int)threadIdx.x < nrow) {
+        *reinterpret_cast<float2*>(ws_ml + (orow(threadIdx.x) * splits + split) * 2) = make_float2(-INFINITY, 0.f);
+      }
+      return;
+    }
+  } else if (hi <= lo) {  // a key range past t, or a guarded position: no loads, R empty partials
     if (splits == 1) {
       if (wave == 0 && grp == 0) {
         const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -251,51 +310,82 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
     return;
   }
 
-  // the row of position t (hi > lo here, so t_ok: PAGED, et is a block of the pool)
-  size_t trow = (size_t)t;
-  if constexpr (PAGED) trow = ((((size_t)et * KVH + kvh) << pp.shift) + (t & bmask));
   float q[R][8];
-  float kt[8];  // the token's own k exactly as the cache holds it
-#pragma unroll
-  for (int r = 0; r < R; ++r) load8<T>(qrow + r * D + gl * 8, q[r]);
-  load8<T>(knew + gl * 8, kt);
-  if constexpr (EXT) {
-    if (rot) {
-      const int chunk = D / rot_dims, half = chunk >> 1;
-      const bool left = ((gl * 8) % chunk) < half;
-      float c[8], s[8];
-      load8<float>(rot + (size_t)b * D + gl * 8, c);
-      load8<float>(rot + ((size_t)B + b) * D + gl * 8, s);
-#pragma unroll
-      for (int r = 0; r < R; ++r) rotate8<T>(qrow + r * D, gl * 8, half, left, c, s, q[r]);
-      rotate8<T>(knew, gl * 8, half, left, c, s, kt);
-      if constexpr (!Q8) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) kt[i] = Cvt<T>::to(Cvt<T>::from(kt[i]));  // rounded once
-      }
-    }
-  }
+  [[maybe_unused]] float kt[8];  // the token's own k exactly as the cache holds it
   float qscale = scale;
   [[maybe_unused]] float vdq = 1.f;
   [[maybe_unused]] uint2 ktq, vtq;  // Q8: the token's own k / v as the bytes the cache holds
-  if constexpr (Q8) {
-    const int plane = (qp.bstride ? B : 1) * KVH;
-    const float* sp = qp.scales + (size_t)b * qp.bstride + kvh;
-    qscale *= sp[2 * plane];  // k dequant rides on the q rows
-    vdq = sp[3 * plane];
-    float vt[8];
-    load8<T>(vnew + gl * 8, vt);
-    ktq = quant8(kt, sp[0], qp.round_type, qp.qmax, qp.qmin);
-    vtq = quant8(vt, sp[plane], qp.round_type, qp.qmax, qp.qmin);
-    if (t < hi && wave == 0 && grp == 0) {  // append: one 8-byte store per lane and row
-      *reinterpret_cast<uint2*>(kc + trow * D + gl * 8) = ktq;
-      *reinterpret_cast<uint2*>(vc + trow * D + gl * 8) = vtq;
+  if constexpr (MULTI) {
+    // the R query rows, each rotated with its own token's cos / sin (rot is [2, B, NT, D]); a
+    // padded row (token >= NT) is a zero query whose result is never posted. The new k / v rows
+    // are the tail's business, after the loop.
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const int j = i >> rsh;
+      if (j < NT) {
+        const T* qr = qkv + (((size_t)b * NT + j) * rows + h0 + (i & rmask)) * D;
+        load8<T>(qr + gl * 8, q[i]);
+        if (rot) {
+          const int chunk = D / rot_dims, half = chunk >> 1;
+          const bool left = ((gl * 8) % chunk) < half;
+          float c[8], s[8];
+          load8<float>(rot + ((size_t)b * NT + j) * D + gl * 8, c);
+          load8<float>(rot + (((size_t)B + b) * NT + j) * D + gl * 8, s);
+          rotate8<T>(qr, gl * 8, half, left, c, s, q[i]);
+        }
+      } else {
+#pragma unroll
+        for (int d = 0; d < 8; ++d) q[i][d] = 0.f;
+      }
     }
-  } else if (t < hi && wave == 0 && grp == 0) {  // append the new token (hi > lo here, so t_ok and t >= lo)
-    float v[8];
-    store8<T>(kc + trow * D + gl * 8, kt);
-    load8<T>(vnew + gl * 8, v);
-    store8<T>(vc + trow * D + gl * 8, v);
+    if constexpr (Q8) {
+      const int plane = (qp.bstride ? B : 1) * KVH;
+      const float* sp = qp.scales + (size_t)b * qp.bstride + kvh;
+      qscale *= sp[2 * plane];  // k dequant rides on the q rows
+      vdq = sp[3 * plane];
+    }
+  } else {
+    // the row of position t (hi > lo here, so t_ok: PAGED, et is a block of the pool)
+    size_t trow = (size_t)t;
+    if constexpr (PAGED) trow = ((((size_t)et * KVH + kvh) << pp.shift) + (t & bmask));
+#pragma unroll
+    for (int r = 0; r < R; ++r) load8<T>(qrow + r * D + gl * 8, q[r]);
+    load8<T>(knew + gl * 8, kt);
+    if constexpr (EXT) {
+      if (rot) {
+        const int chunk = D / rot_dims, half = chunk >> 1;
+        const bool left = ((gl * 8) % chunk) < half;
+        float c[8], s[8];
+        load8<float>(rot + (size_t)b * D + gl * 8, c);
+        load8<float>(rot + ((size_t)B + b) * D + gl * 8, s);
+#pragma unroll
+        for (int r = 0; r < R; ++r) rotate8<T>(qrow + r * D, gl * 8, half, left, c, s, q[r]);
+        rotate8<T>(knew, gl * 8, half, left, c, s, kt);
+        if constexpr (!Q8) {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) kt[i] = Cvt<T>::to(Cvt<T>::from(kt[i]));  // rounded once
+        }
+      }
+    }
+    if constexpr (Q8) {
+      const int plane = (qp.bstride ? B : 1) * KVH;
+      const float* sp = qp.scales + (size_t)b * qp.bstride + kvh;
+      qscale *= sp[2 * plane];  // k dequant rides on the q rows
+      vdq = sp[3 * plane];
+      float vt[8];
+      load8<T>(vnew + gl * 8, vt);
+      ktq = quant8(kt, sp[0], qp.round_type, qp.qmax, qp.qmin);
+      vtq = quant8(vt, sp[plane], qp.round_type, qp.qmax, qp.qmin);
+      if (t < hi && wave == 0 && grp == 0) {  // append: one 8-byte store per lane and row
+        *reinterpret_cast<uint2*>(kc + trow * D + gl * 8) = ktq;
+        *reinterpret_cast<uint2*>(vc + trow * D + gl * 8) = vtq;
+      }
+    } else if (t < hi && wave == 0 && grp == 0) {  // append the new token (hi > lo here, so t_ok and t >= lo)
+      float v[8];
+      store8<T>(kc + trow * D + gl * 8, kt);
+      load8<T>(vnew + gl * 8, v);
+      store8<T>(vc + trow * D + gl * 8, v);
+    }
   }
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -355,10 +445,12 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
         }
         kr[u] = *reinterpret_cast<const uint2*>(kc + row * D + gl * 8);
         vr[u] = *reinterpret_cast<const uint2*>(vc + row * D + gl * 8);
-        if (kk == t) {  // the token's own row: the quantised registers, not what the slot held
-          kr[u] = ktq;
-          vr[u] = vtq;
-        }
+        if constexpr (!MULTI) {
+          if (kk == t) {  // the token's own row: the quantised registers, not what the slot held
+            kr[u] = ktq;
+            vr[u] = vtq;
+          }
+        }  // MULTI: kk == t only for a bad entry; whatever bytes the slot holds are finite, weight 0
         add[u] = live ? (mrow ? mrow[key] : 0.f) : -INFINITY;
       }
       if constexpr (PAGED) {  // the next iteration's entries, behind this one's row loads
@@ -441,7 +533,9 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
         const T* vp = (kk == t) ? vnew : vc + row * D;
         load8<T>(kp + gl * 8, kx[u]);
         load8<T>(vp + gl * 8, vx[u]);
-        if constexpr (EXT) {  // the token's own key: the (rotated, rounded) registers, not the raw row
+        // MULTI: kk == t only for a bad entry, and the raw qkv rows of token 0 then stand in with
+        // weight 0 (finite, unlike what the slot at t may hold)
+        if constexpr (EXT && !MULTI) {  // the token's own key: the (rotated, rounded) registers, not the raw row
           if (kk == t) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) kx[u][i] = kt[i];
@@ -482,6 +576,73 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
     }
   }
 
+  if constexpr (MULTI) {
+    // the tail: lane group j of the workgroup that owns t takes new token j from the qkv buffer
+    // (kWaves * KPW >= 8 >= NT groups): rotate k with token j's cos / sin, round or quantise it,
+    // append the row at t + j, and score it as one more key against the R rows. A row of an
+    // earlier token does not see it (weight 0): the causal rule among the new tokens.
+    const int j = wave * KPW + grp;
+    if (tail && j < NT) {
+      const T* kn = qkv + (((size_t)b * NT + j) * rows + H + kvh) * D;
+      const int pos = t + j;  // t_ok: pos < L, inside the mask, and PAGED: its block is et or et1
+      float kj[8], vj[8];
+      load8<T>(kn + gl * 8, kj);
+      load8<T>(kn + (size_t)KVH * D + gl * 8, vj);
+      if (rot) {
+        const int chunk = D / rot_dims, half = chunk >> 1;
+        const bool left = ((gl * 8) % chunk) < half;
+        float c[8], s[8];
+        load8<float>(rot + ((size_t)b * NT + j) * D + gl * 8, c);
+        load8<float>(rot + (((size_t)B + b) * NT + j) * D + gl * 8, s);
+        rotate8<T>(kn, gl * 8, half, left, c, s, kj);
+        if constexpr (!Q8) {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) kj[i] = Cvt<T>::to(Cvt<T>::from(kj[i]));  // rounded once
+        }
+      }
+      size_t prow = (size_t)pos;
+      if constexpr (PAGED) {
+        const int e = (pos >> pp.shift) == (t >> pp.shift) ? et : et1;
+        prow = (((size_t)e * KVH + kvh) << pp.shift) + (pos & bmask);
+      }
+      if constexpr (Q8) {
+        const int plane = (qp.bstride ? B : 1) * KVH;
+        const float* sp = qp.scales + (size_t)b * qp.bstride + kvh;
+        const uint2 kq = quant8(kj, sp[0], qp.round_type, qp.qmax, qp.qmin);
+        const uint2 vq = quant8(vj, sp[plane], qp.round_type, qp.qmax, qp.qmin);
+        *reinterpret_cast<uint2*>(kc + prow * D + gl * 8) = kq;
+        *reinterpret_cast<uint2*>(vc + prow * D + gl * 8) = vq;
+        unpack8(kq, kj);  // scored as the stored levels
+        unpack8(vq, vj);
+      } else {
+        store8<T>(kc + prow * D + gl * 8, kj);
+        store8<T>(vc + prow * D + gl * 8, vj);
+      }
+      const float add = mrow ? mrow[pos] : 0.f;
+#pragma unroll
+      for (int i = 0; i < R; ++i) {
+        f2 d2 = {0.f, 0.f};
+#pragma unroll
+        for (int d = 0; d < 8; d += 2) d2 += f2{q[i][d], q[i][d + 1]} * f2{kj[d], kj[d + 1]};
+        float s = group_sum<G>(d2.x + d2.y);
+        if constexpr (Q8) {  // the offset term of the row, as in the loop
+          float sum = 0.f;
+#pragma unroll
+          for (int d = 0; d < 8; ++d) sum += q[i][d];
+          s -= 128.f * group_sum<G>(sum);
+        }
+        s = (i >> rsh) < j ? -INFINITY : s + add;
+        const float mn = fmaxf(m[i], s);
+        const float ms = (mn == -INFINITY) ? 0.f : mn;
+        const float c = __expf(m[i] - ms), p = __expf(s - ms);
+        l[i] = l[i] * c + p;
+#pragma unroll
+        for (int d = 0; d < 8; ++d) acc[i][d] = acc[i][d] * c + p * vj[d];
+        m[i] = mn;
+      }
+    }
+  }
+
   // merge the KPW key groups of this wave (lanes gl, gl+G, ...)
 #pragma unroll
   for (int o = G; o < 64; o <<= 1) {
@@ -509,6 +670,9 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
   __syncthreads();
   const int r = wave * KPW + grp;  // this lane group's query head
   if (r >= R) return;
+  if constexpr (MULTI) {
+    if ((r >> rsh) >= NT) return;  // a padded row: never stored, no partial posted
+  }
   float fm = s_ml[0][r][0], fl = s_ml[0][r][1], fa[8];
   load8<float>(&s_acc[0][r][gl * 8], fa);
   for (int w = 1; w < kWaves; ++w) {
@@ -524,10 +688,10 @@ __global__ void __launch_bounds__(kWaves * 64) mmha_split_k(
     const float inv = fl > 0.f ? 1.f / fl : 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) fa[i] *= inv;
-    store8<T>(out + ((size_t)b * H + h0 + r) * D + gl * 8, fa);
+    store8<T>(out + (MULTI ? orow(r) : (size_t)b * H + h0 + r) * D + gl * 8, fa);
     return;
   }
-  const size_t w = w0 + (size_t)r * splits;
+  const size_t w = MULTI ? orow(r) * splits + split : w0 + (size_t)r * splits;
   store8<float>(ws_acc + w * D + gl * 8, fa);
   if (gl == 0) *reinterpret_cast<float2*>(ws_ml + w * 2) = make_float2(fm, fl);
 }
@@ -571,6 +735,7 @@ struct Args {
   float qmax, qmin;
   const int* tables;  // paged cache: [B, MB] int32, else null
   int NB, MB, shift;
+  int n_tok;  // new tokens per sequence (1: the single-token kernels)
 };
 
 template <bool Q8> QParams<Q8> qparams(const Args& a);
@@ -583,6 +748,15 @@ template <bool PAGED> PParams<PAGED> pparams(const Args& a);
 template <> PParams<false> pparams<false>(const Args&) { return {}; }
 template <> PParams<true> pparams<true>(const Args& a) { return {a.tables, a.NB, a.MB, a.shift}; }
 
+template <bool Q8, bool PAGED, bool MULTI = false>
+XParams<Q8, PAGED, MULTI> xparams(const Args& a, int rshift = 0) {
+  XParams<Q8, PAGED, MULTI> xp;
+  static_cast<QParams<Q8>&>(xp) = qparams<Q8>(a);
+  static_cast<PParams<PAGED>&>(xp) = pparams<PAGED>(a);
+  if constexpr (MULTI) static_cast<MParams<true>&>(xp) = {a.n_tok, rshift};
+  return xp;
+}
+
 template <typename T, int D, int R, bool EXT, bool Q8 = false, bool PAGED = false>
 int launch(const Args& a) {
   const int keys = a.t_dev ? a.L : a.t + 1;  // device position: splits cover the whole cache
@@ -592,10 +766,51 @@ int launch(const Args& a) {
   hipLaunchKernelGGL((mmha_split_k<T, D, R, EXT, Q8, PAGED>), dim3(a.splits, a.KVH, a.B), dim3(kWaves * 64), 0, a.s,
                      (const T*)a.qkv, (std::conditional_t<Q8, uint8_t, T>*)a.cache, a.mask, ws_ml, ws_acc, (T*)a.out,
                      a.B, a.KVH, a.L, a.t, a.t_dev, per, a.mask_len, a.scale, a.seq_lens, a.rot, a.rot_dims,
-                     XParams<Q8, PAGED>{qparams<Q8>(a), pparams<PAGED>(a)});
+                     xparams<Q8, PAGED>(a));
   if (a.splits > 1)
     hipLaunchKernelGGL((mmha_combine_k<T, D>), dim3(a.H, a.B), dim3(D), 0, a.s, ws_ml, ws_acc, (T*)a.out, a.splits);
   return 0;
+}
+
+// n_tok > 1 tokens per sequence: NQ query rows per K/V head; partials and output as if there
+// were n_tok*H heads, so the combine kernel runs unchanged on grid (n_tok*H, B)
+template <typename T, int D, int NQ, bool Q8, bool PAGED>
+int launch_multi(const Args& a, int rshift) {
+  const int keys = a.t_dev ? a.L : a.t + a.n_tok;  // device position: splits cover the whole cache
+  const int per = (keys + a.splits - 1) / a.splits;
+  const int HT = a.H * a.n_tok;
+  float* ws_ml = a.ws;
+  float* ws_acc = a.ws + (((size_t)a.B * HT * a.splits * 2 + 3) / 4) * 4;  // 16-B aligned
+  hipLaunchKernelGGL((mmha_split_k<T, D, NQ, true, Q8, PAGED, true>), dim3(a.splits, a.KVH, a.B), dim3(kWaves * 64),
+                     0, a.s, (const T*)a.qkv, (std::conditional_t<Q8, uint8_t, T>*)a.cache, a.mask, ws_ml, ws_acc,
+                     (T*)a.out, a.B, a.KVH, a.L, a.t, a.t_dev, per, a.mask_len, a.scale, a.seq_lens, a.rot,
+                     a.rot_dims, xparams<Q8, PAGED, true>(a, rshift));
+  if (a.splits > 1)
+    hipLaunchKernelGGL((mmha_combine_k<T, D>), dim3(HT, a.B), dim3(D), 0, a.s, ws_ml, ws_acc, (T*)a.out, a.splits);
+  return 0;
+}
+
+template <typename T, int D, int NQ>
+int launch_multi_x(const Args& a, int rshift) {
+  if (a.tables)
+    return a.scales ? launch_multi<T, D, NQ, true, true>(a, rshift) : launch_multi<T, D, NQ, false, true>(a, rshift);
+  return a.scales ? launch_multi<T, D, NQ, true, false>(a, rshift) : launch_multi<T, D, NQ, false, false>(a, rshift);
+}
+
+// the ratio R = H / KVH and Tp = n_tok rounded up to a power of two give NQ = R * Tp in {2, 4, 8}
+template <typename T, int D>
+int launch_multi_r(const Args& a) {
+  const int ratio = a.H / a.KVH;
+  if (ratio > 8 || (ratio & (ratio - 1)) != 0 || a.n_tok > 8) return -1;
+  int tp = 2;
+  while (tp < a.n_tok) tp <<= 1;
+  const int rshift = __builtin_ctz((unsigned)ratio);
+  switch (ratio * tp) {
+    case 2: return launch_multi_x<T, D, 2>(a, rshift);
+    case 4: return launch_multi_x<T, D, 4>(a, rshift);
+    case 8: return launch_multi_x<T, D, 8>(a, rshift);
+    default: return -1;  // more than 8 query rows per K/V row
+  }
 }
 
 template <typename T, int D>
@@ -629,6 +844,14 @@ int launch_r(const Args& a) {
 
 template <typename T>
 int launch_d(int D, const Args& a) {
+  if (a.n_tok > 1) {
+    switch (D) {
+      case 64: return launch_multi_r<T, 64>(a);
+      case 128: return launch_multi_r<T, 128>(a);
+      case 256: return launch_multi_r<T, 256>(a);
+      default: return -1;
+    }
+  }
   switch (D) {
     case 64: return launch_r<T, 64>(a);
     case 128: return launch_r<T, 128>(a);
@@ -641,9 +864,9 @@ int launch_d(int D, const Args& a) {
 // logical capacity either way)
 int decode(const Args& a, int D, int dt, int cache_dt) {
   if (a.splits < 1 || a.B < 1 || a.B > 65535 || a.KVH < 1 || a.KVH > 65535 || a.H < a.KVH || a.H % a.KVH != 0 ||
-      a.L < 1)
+      a.L < 1 || a.n_tok < 1)
     return -1;
-  if (!a.t_dev && (a.t < 0 || a.t >= a.L || (a.mask && a.mask_len < a.t + 1))) return -1;
+  if (!a.t_dev && (a.t < 0 || a.t > a.L - a.n_tok || (a.mask && a.mask_len < a.t + a.n_tok))) return -1;
   if (a.rot && (a.rot_dims < 1 || D % (16 * a.rot_dims) != 0)) return -1;  // a half chunk is whole 8-dim lanes
   if (cache_dt == kCacheU8) {  // a row piece is one aligned 8-byte access
     if (!a.scales || (a.scale_bstride != 0 && a.scale_bstride != a.KVH) || (a.round_type != 0 && a.round_type != 1) ||
@@ -690,7 +913,7 @@ int pra_mmha_decode(const void* qkv, void* cache, const float* mask, float* ws, 
                     const int* seq_lens, const float* rot, int rot_dims, hipStream_t s, int cache_dt,
                     const float* scales, int scale_batch_stride, int round_type, float qmax, float qmin) {
   const Args a{qkv, cache, mask, ws, out, B, H, KVH, L, t, t_dev, splits, mask_len, scale, seq_lens, rot,
-               rot_dims, s, scales, scale_batch_stride, round_type, qmax, qmin, nullptr, 0, 0, 0};
+               rot_dims, s, scales, scale_batch_stride, round_type, qmax, qmin, nullptr, 0, 0, 0, 1};
   return decode(a, D, dt, cache_dt);
 }
 
@@ -712,7 +935,34 @@ int pra_mmha_decode_paged(const void* qkv, void* cache, const float* mask, float
     return -1;
   const int shift = __builtin_ctz((unsigned)BS);
   const Args a{qkv, cache, mask, ws, out, B, H, KVH, MB * BS, t, t_dev, splits, mask_len, scale, seq_lens, rot,
-               rot_dims, s, scales, scale_batch_stride, round_type, qmax, qmin, block_tables, NB, MB, shift};
+               rot_dims, s, scales, scale_batch_stride, round_type, qmax, qmin, block_tables, NB, MB, shift, 1};
+  return decode(a, D, dt, cache_dt);
+}
+
+// n_tok new tokens per sequence in one pass over the cache, equal to n_tok consecutive
+// single-token steps: qkv [B, n_tok, H + 2*KVH, D], out [B, n_tok, H, D]; token j of sequence b
+// sits at position t_b + j, is appended there and attends to [0, t_b + j]. rot is
+// [2, B, n_tok, D] (row j: the cos / sin of position t_b + j); the mask row is shared by the
+// tokens. The arguments are pra_mmha_decode_paged's; a null block_tables means the contiguous
+// cache [2, B, KVH, L, D] with L = MB*BS (NB unused, no condition on BS). splits come from
+// pra_mmha_splits(B, KVH, t + n_tok - 1) (device position: L - 1) and ws holds
+// B*n_tok*H*splits*(2 + D) + 4 floats. A sequence is guarded as a whole (n_tok zero rows, no
+// write) when t_b < 0, t_b + n_tok > L, t_b exceeds the host bound t, the mask is shorter than
+// t_b + n_tok, or (paged) the table entry of a block holding one of its new positions is outside
+// [0, NB). Returns non-zero for n_tok < 1, for more than 8 query rows per K/V row
+// ((H / KVH) * n_tok rounded up to a power of two > 8), and for everything the single-token
+// entries refuse; n_tok = 1 is the single-token step.
+int pra_mmha_decode_multi(const void* qkv, void* cache, const float* mask, float* ws, void* out, int B, int H,
+                          int KVH, int NB, int BS, int MB, int D, int t, const int* t_dev, int splits,
+                          int mask_len, float scale, int dt, const int* seq_lens, const float* rot, int rot_dims,
+                          hipStream_t s, int cache_dt, const float* scales, int scale_batch_stride, int round_type,
+                          float qmax, float qmin, const int* block_tables, int n_tok) {
+  if (n_tok < 1 || BS < 1 || MB < 1 || (long long)MB * BS > 0x7fffffffLL) return -1;
+  if (block_tables && (BS < 16 || (BS & (BS - 1)) != 0 || NB < 1)) return -1;
+  const int shift = block_tables ? __builtin_ctz((unsigned)BS) : 0;
+  const Args a{qkv, cache, mask, ws, out, B, H, KVH, MB * BS, t, t_dev, splits, mask_len, scale, seq_lens, rot,
+               rot_dims, s, scales, scale_batch_stride, round_type, qmax, qmin, block_tables,
+               block_tables ? NB : 0, MB, shift, n_tok};
   return decode(a, D, dt, cache_dt);
 }
 }

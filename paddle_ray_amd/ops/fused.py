@@ -1301,6 +1301,220 @@ def _mmha_decode_paged(qkv, pool, time_step, mask, seq_lens, rotary, rotary_dims
                       **({} if quant is None else {'quant': quant}))
 
 
+# --- several new tokens per sequence in one pass over the cache ---------------------------------
+MULTI_MAX_ROWS = 8       # query rows per K/V row the HIP multi-token kernel is built for
+
+
+def _pow2_at_least(n, least=2):
+    p = least
+    while p < n:
+        p *= 2
+    return p
+
+
+@R.register_kernel('mmha_decode_multi', 'ref')
+def _mmha_multi_ref(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0, quant=None, tables=None):
+    """The definition of the multi-token step: the all-or-nothing guard, then T calls of the
+    single-token oracle at ``seq_lens + j`` with token j's row and rotary. ``tables`` (int
+    [B, MB]) makes ``cache`` the block pool."""
+    B, T = qkv.shape[0], qkv.shape[1]
+    paged = tables is not None
+    L = tables.shape[1] * cache.shape[3] if paged else cache.shape[3]
+    dev_t = isinstance(t, torch.Tensor)
+    tt = int(t.reshape(-1)[0]) if dev_t else int(t)
+    bound = L if dev_t else tt                                    # a tensor position: no batch-wide bound
+    lens = [tt] * B if seq_lens is None else [int(n) for n in seq_lens.reshape(-1).tolist()]
+    mlen = None if mask is None else mask.reshape(B, -1).shape[1]
+    ok = [0 <= n <= bound and n + T <= L and (mlen is None or mlen >= n + T) for n in lens]
+    if paged:                                                     # both blocks of the T new positions
+        NB, BS = cache.shape[1], cache.shape[3]
+        rows = tables.tolist()
+        ok = [g and all(0 <= rows[b][p // BS] < NB for p in (lens[b], lens[b] + T - 1))
+              for b, g in enumerate(ok)]
+    out = None
+    for j in range(T):
+        # a guarded sequence sits at L in every call: out of range for the oracle, zeros, no write
+        sl = torch.tensor([n + j if ok[b] else L for b, n in enumerate(lens)], dtype=torch.int32,
+                          device=qkv.device)
+        tj = t if dev_t else tt + j
+        rj = None if rotary is None else rotary[:, :, j].contiguous()
+        row = qkv[:, j].contiguous()
+        if paged:
+            o = _mmha_paged_ref(row, cache, tj, mask, tables, seq_lens=sl, rotary=rj, rotary_dims=rotary_dims,
+                                quant=quant)
+        else:
+            o = _mmha_ref(row, cache, tj, mask, seq_lens=sl, rotary=rj, rotary_dims=rotary_dims, quant=quant)
+        if out is None:
+            out = torch.zeros(B, T, o.shape[1], o.shape[2], dtype=o.dtype, device=o.device)
+        out[:, j] = o
+    return out
+
+
+@R.register_kernel('mmha_decode_multi', 'hip', dtypes=_FLOATS)
+def _mmha_multi_hip(qkv, cache, t, mask, seq_lens=None, rotary=None, rotary_dims=0, quant=None, tables=None):
+    B, T, N, D = qkv.shape
+    KVH = cache.shape[2]
+    H = N - 2 * KVH
+    ratio = H // KVH
+    if ratio not in (1,) + GQA_RATIOS or ratio * _pow2_at_least(T) > MULTI_MAX_ROWS:
+        raise ValueError(f"mmha_decode_multi: {T} tokens of {H} query heads over {KVH} K/V heads are "
+                         f"{ratio} x {_pow2_at_least(T)} query rows per K/V row (the token count rounded "
+                         f"up to a power of two); the HIP kernel supports ratios {(1,) + GQA_RATIOS} and at "
+                         f"most {MULTI_MAX_ROWS} rows")
+    if tables is None:
+        L, NB, BS, MB = cache.shape[3], 0, cache.shape[3], 1
+    else:
+        NB, BS, MB = cache.shape[1], cache.shape[3], tables.shape[1]
+        L = MB * BS
+        if BS < 16 or BS & (BS - 1):
+            raise ValueError(f"mmha_decode_multi: block size {BS} is not supported by the HIP kernel (a "
+                             "power of two >= 16)")
+        if not (tables.is_cuda and tables.dtype == torch.int32 and tables.is_contiguous() and
+                tables.dim() == 2 and tables.shape[0] == B):
+            raise ValueError(f"mmha_decode_multi: block_tables must be a contiguous CUDA int32 [{B}, MB] tensor")
+    t_dev = None
+    if isinstance(t, torch.Tensor):  # device position (HIP-graph decode loops): read in-kernel
+        if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+            raise ValueError("mmha_decode_multi: a tensor time_step must be a CUDA int32 tensor")
+        t_dev, t = t, 0
+    cache_ok = cache.dtype == qkv.dtype if quant is None else \
+        (cache.dtype == torch.uint8 and cache.is_cuda and cache.data_ptr() % 8 == 0)
+    if not (qkv.is_contiguous() and cache.is_contiguous() and cache_ok and
+            (tuple(cache.shape) == (2, B, KVH, L, D) if tables is None else
+             tuple(cache.shape[2:]) == (KVH, BS, D)) and D in (64, 128, 256) and
+            (t_dev is not None or 0 <= t <= L - T)):
+        raise ValueError(f"mmha_decode_multi: qkv {tuple(qkv.shape)} / cache {tuple(cache.shape)} / "
+                         f"t={t} not supported by the HIP kernel")
+    if seq_lens is not None and not (seq_lens.is_cuda and seq_lens.dtype == torch.int32 and
+                                     seq_lens.is_contiguous() and seq_lens.numel() == B):
+        raise ValueError(f"mmha_decode_multi: seq_lens must be a contiguous CUDA int32 [{B}] tensor")
+    if rotary is not None:
+        if not rotary_in_kernel(D, rotary_dims):
+            raise ValueError(f"mmha_decode_multi: head_dim {D} with rotary_dims={rotary_dims} is not "
+                             "supported by the HIP kernel (half a chunk must be a multiple of 8)")
+        if not (rotary.is_cuda and rotary.dtype == torch.float32 and rotary.is_contiguous() and
+                tuple(rotary.shape) == (2, B, T, D)):
+            raise ValueError(f"mmha_decode_multi: rotary must be a contiguous CUDA fp32 [2, {B}, {T}, {D}] "
+                             "tensor")
+    # splits are sized for t + T keys; a device position makes them cover L
+    splits = _native.lib().mmha_splits(B, KVH, L - 1 if t_dev is not None else t + T - 1)
+    ws = torch.empty(B * T * H * splits * (2 + D) + 4 if splits > 1 else 4, device=qkv.device,
+                     dtype=torch.float32)
+    out = torch.empty(B, T, H, D, device=qkv.device, dtype=qkv.dtype)
+    mlen = 0
+    if mask is not None:
+        mask = mask.reshape(B, -1).float().contiguous()
+        mlen = mask.shape[1]
+        if t_dev is None and mlen < t + T:
+            raise ValueError(f"mmha_decode_multi: mask covers {mlen} positions, need {t + T}")
+    if quant is not None:
+        scales, bstride, round_type, qmax, qmin = quant
+        if not (scales.is_cuda and scales.dtype == torch.float32 and scales.is_contiguous() and
+                tuple(scales.shape) == (4, B if bstride else 1, KVH) and bstride in (0, KVH)):
+            raise ValueError(f"mmha_decode_multi: the packed cache scales must be a contiguous CUDA fp32 "
+                             f"[4, 1 or {B}, {KVH}] tensor")
+        cache_dt, scales_ptr = _CACHE_U8, _ptr(scales)
+    else:
+        cache_dt, scales_ptr, bstride, round_type, qmax, qmin = _dt(qkv), 0, 0, 1, 127.0, -127.0
+    _native.lib().mmha_decode_multi(_ptr(qkv), _ptr(cache), _ptr(mask) if mask is not None else 0,
+                                    _ptr(ws), _ptr(out), B, H, KVH, NB, BS, MB, D, int(t),
+                                    _ptr(t_dev) if t_dev is not None else 0, splits, mlen,
+                                    1.0 / math.sqrt(D), _dt(qkv),
+                                    _ptr(seq_lens) if seq_lens is not None else 0,
+                                    _ptr(rotary) if rotary is not None else 0, int(rotary_dims),
+                                    _stream(), cache_dt, scales_ptr, bstride, round_type, qmax, qmin,
+                                    _ptr(tables) if tables is not None else 0, T)
+    return out
+
+
+def mmha_decode_multi(qkv, cache, time_step, mask=None, seq_lens=None, rotary=None, rotary_dims=0,
+                      cache_k_quant_scales=None, cache_v_quant_scales=None, cache_k_dequant_scales=None,
+                      cache_v_dequant_scales=None, quant_round_type=1, quant_max_bound=127.0,
+                      quant_min_bound=-127.0, block_tables=None):
+    """One decode step with T new tokens per sequence; equal to T consecutive ``mmha_decode``
+    steps, in one pass over the cache. ``qkv`` is [B, T, H + 2*KVH, D] (KVH is the cache's; KVH = H
+    is plain multi-head attention) and the result [B, T, H, D]. Token j of sequence b sits at
+    position ``t_b + j`` (``t_b = seq_lens[b]``, or ``time_step`` without ``seq_lens``): its K/V
+    are appended there, under the caching rule of ``mmha_decode`` for a float or a ``uint8``
+    cache, and it attends to [0, t_b + j]. The additive ``mask`` [B, mask_len] is shared by the T
+    tokens; the causal rule among them is built in. ``rotary`` is [2, B, T, D], row j the cos /
+    sin of position ``t_b + j``. ``cache``, the quantisation arguments and ``block_tables`` are
+    ``mmha_decode``'s.
+
+    Host positions are validated (0 <= t_b <= time_step, time_step + T <= L, and with a host
+    table: every block covering [0, t_b + T) in [0, NB), no two sequences appending to the same
+    block over their T positions). Device values are not synced; a sequence is then guarded as a
+    whole, T zero rows and no write at all, when t_b < 0, t_b + T > L, t_b exceeds a host
+    ``time_step``, the mask is shorter than t_b + T, or a block holding one of its T positions
+    has a table entry outside [0, NB). On the GPU (H / KVH) * Tp must not exceed
+    ``MULTI_MAX_ROWS``, Tp being T rounded up to a power of two."""
+    if qkv.dim() != 4 or qkv.shape[1] < 1:
+        raise ValueError(f"mmha_decode_multi: qkv must be [B, T, H + 2*KVH, D] with T >= 1, got "
+                         f"{tuple(qkv.shape)}")
+    B, T, N, D = qkv.shape
+    if not isinstance(time_step, torch.Tensor):
+        time_step = int(time_step)
+    paged = block_tables is not None
+    if cache.dim() != 5 or cache.shape[0] != 2 or cache.shape[4] != D or (not paged and cache.shape[1] != B):
+        raise ValueError(f"mmha_decode_multi: cache {tuple(cache.shape)} does not fit qkv {tuple(qkv.shape)}; "
+                         f"need {'the block pool [2, NB, KVH, BS, D]' if paged else '[2, B, KVH, L, D]'}")
+    KVH = cache.shape[2]
+    H = N - 2 * KVH
+    if H <= 0 or H % KVH != 0:
+        raise ValueError(f"mmha_decode_multi: qkv has {N} head rows and the cache {KVH} K/V heads; "
+                         f"{N} - 2*{KVH} query heads must be a positive multiple of {KVH}")
+    tables = None
+    if paged:
+        tables = torch.as_tensor(block_tables)
+        if tables.dim() != 2 or tables.shape[0] != B or tables.shape[1] < 1 or tables.dtype.is_floating_point:
+            raise ValueError(f"mmha_decode_multi: block_tables must be an integer [{B}, MB] table, got "
+                             f"{tuple(tables.shape)} {tables.dtype}")
+    L = tables.shape[1] * cache.shape[3] if paged else cache.shape[3]
+    quant = _kv_quant_args(B, cache, cache_k_quant_scales, cache_v_quant_scales, cache_k_dequant_scales,
+                           cache_v_dequant_scales, quant_round_type, quant_max_bound, quant_min_bound,
+                           qkv.device)
+    # as in mmha_decode: a CUDA position is never synced, and with a table any tensor position is
+    # a device-style one
+    host_t = not isinstance(time_step, torch.Tensor) or (not paged and not time_step.is_cuda)
+    host_lens = seq_lens is None or not (isinstance(seq_lens, torch.Tensor) and seq_lens.is_cuda)
+    lens = None
+    if seq_lens is not None:
+        seq_lens = torch.as_tensor(seq_lens).reshape(-1)
+        if seq_lens.numel() != B:
+            raise ValueError(f"mmha_decode_multi: seq_lens has {seq_lens.numel()} entries for batch {B}")
+    if host_t and host_lens:
+        ts = int(time_step)
+        lens = [ts] * B if seq_lens is None else [int(n) for n in seq_lens.tolist()]
+        if not (all(0 <= n <= ts for n in lens) and ts + T <= L):
+            raise ValueError(f"mmha_decode_multi: need 0 <= seq_lens <= time_step and time_step + {T} <= "
+                             f"{L}, got seq_lens={lens} time_step={ts}")
+    if paged:
+        if lens is not None and not tables.is_cuda:
+            NB, BS, rows, owner = cache.shape[1], cache.shape[3], tables.tolist(), {}
+            for b, n in enumerate(lens):
+                bad = [e for e in rows[b][:(n + T - 1) // BS + 1] if not 0 <= e < NB]
+                if bad:
+                    raise ValueError(f"mmha_decode_multi: block_tables[{b}] covers positions [0, {n + T}) "
+                                     f"with entry {bad[0]}, outside the pool's [0, {NB})")
+                for e in {rows[b][n // BS], rows[b][(n + T - 1) // BS]}:
+                    if owner.setdefault(e, b) != b:
+                        raise ValueError(f"mmha_decode_multi: two sequences append to the same block ({e}, "
+                                         f"sequences {owner[e]} and {b}); only blocks that are read may "
+                                         "be shared")
+        tables = tables.to(device=qkv.device, dtype=torch.int32).contiguous()
+    if seq_lens is not None:
+        seq_lens = seq_lens.to(device=qkv.device, dtype=torch.int32).contiguous()
+    if rotary is not None:
+        if isinstance(rotary, (tuple, list)):
+            rotary = torch.stack([torch.as_tensor(r).reshape(B, T, D) for r in rotary])
+        if int(rotary_dims) < 1:
+            raise ValueError("mmha_decode_multi: rotary needs rotary_dims >= 1")
+        rotary = rotary.reshape(2, B, T, D).to(device=qkv.device, dtype=torch.float32).contiguous()
+    return R.dispatch('mmha_decode_multi', qkv, qkv.contiguous(), cache, time_step, mask,
+                      seq_lens=seq_lens, rotary=rotary, rotary_dims=int(rotary_dims), quant=quant,
+                      tables=tables)
+
+
 # =============================================================================
 # bias + GELU
 # =============================================================================

@@ -3,9 +3,10 @@ the same KV cache, a ragged batch (per-sequence seq_lens) next to its padded-and
 grouped-query attention next to the expanded multi-head cache and the byte floor, end-to-end
 FusedMultiTransformer decode steps/s, and the 8-bit KV cache next to the bf16 one (kernel rows
 and the graph decoder), and the paged cache (a block pool behind shuffled block tables) next to
-the contiguous cache of the same logical contents.
+the contiguous cache of the same logical contents, and the multi-token step (T new tokens per
+sequence in one cache pass) next to T single-token steps on the same cache.
 
-usage: python scripts/decode_bench.py [--quick] [--sections plain,ragged,gqa,e2e,q8,paged]"""
+usage: python scripts/decode_bench.py [--quick] [--sections plain,ragged,gqa,e2e,q8,paged,multi]"""
 import argparse
 import json
 import math
@@ -49,8 +50,8 @@ def bench_graph(fn, calls=20, reps=10):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--quick', action='store_true')
-    ap.add_argument('--sections', default='plain,ragged,gqa,e2e,q8,paged',
-                    help='comma-separated: plain, ragged, gqa, e2e, q8, paged')
+    ap.add_argument('--sections', default='plain,ragged,gqa,e2e,q8,paged,multi',
+                    help='comma-separated: plain, ragged, gqa, e2e, q8, paged, multi')
     a = ap.parse_args()
     sections = set(a.sections.split(','))
     from paddle_ray_amd.ops import fused as K
@@ -66,6 +67,8 @@ def main():
         q8_rows(K)
     if 'paged' in sections:
         paged_rows(K)
+    if 'multi' in sections:
+        multi_rows(a, K)
 
 
 def plain_rows(a, K):
@@ -264,6 +267,78 @@ def paged_rows(K):
                               contig_graph_TBps=round(nbytes / cg / 1e12, 2),
                               paged_graph_TBps=round(nbytes / pg / 1e12, 2), bit_equal=same)), flush=True)
         del cache, pool
+
+
+def _stats(samples, scale):
+    v = sorted(x * scale for x in samples)
+    return dict(samples=[round(x, 2) for x in (s * scale for s in samples)], median=round(v[len(v) // 2], 2),
+                spread=round(v[-1] - v[0], 2))
+
+
+def multi_rows(a, K, samples=5):
+    # the multi-token step (T new tokens per sequence scored against the cache in one pass) next
+    # to the single-token kernel on the same cache, both replayed from a captured HIP graph,
+    # `samples` samples each. over_single is what T tokens cost in single steps' time;
+    # over_T_single below 1 is the point of the feature: T tokens for less than T steps.
+    D, Bq, BS = 128, 8, 64
+    t, L = 4095, 4096 + BS                      # room for the new tokens, a whole number of blocks
+    for H, KVH, T, kind in ((32, 32, 2, 'bf16'), (32, 32, 4, 'bf16'), (32, 32, 8, 'bf16'), (32, 8, 2, 'bf16'),
+                            (32, 32, 4, 'uint8'), (32, 32, 4, 'paged')):
+        rows = torch.randn(Bq, T, H + 2 * KVH, D, device='cuda', dtype=torch.bfloat16)
+        one = rows[:, 0].contiguous()
+        if H == KVH:
+            one = one.reshape(Bq, 3, H, D)
+        cache = torch.randn(2, Bq, KVH, L, D, device='cuda', dtype=torch.bfloat16)
+        kw = {}
+        if kind == 'uint8':
+            packed = torch.empty(4, 1, KVH, device='cuda')
+            packed[:2] = 127.0 / 4.5
+            packed[2:] = 4.5 / 127.0
+            cache = torch.stack([K.kv_quantize(cache[i], packed[i, 0]) for i in range(2)])
+            kw = dict(cache_k_quant_scales=packed[0, 0], cache_v_quant_scales=packed[1, 0],
+                      cache_k_dequant_scales=packed[2, 0], cache_v_dequant_scales=packed[3, 0])
+        if kind == 'paged':
+            MB = L // BS
+            perm = torch.randperm(Bq * MB, generator=torch.Generator().manual_seed(BS))
+            table = perm.reshape(MB, Bq).t().contiguous().to(device='cuda', dtype=torch.int32)
+            pool = torch.empty(2, Bq * MB, KVH, BS, D, device='cuda', dtype=cache.dtype)
+            pool[:, table.long()] = cache.reshape(2, Bq, KVH, MB, BS, D).permute(0, 1, 3, 2, 4, 5)
+            cache, kw = pool, dict(block_tables=table)
+        with torch.no_grad():
+            single = [bench_graph(lambda: K.mmha_decode(one, cache, t, **kw)) for _ in range(samples)]
+            multi = [bench_graph(lambda: K.mmha_decode_multi(rows, cache, t, **kw)) for _ in range(samples)]
+        s1, sm = _stats(single, 1e6), _stats(multi, 1e6)
+        print(json.dumps(dict(multi=True, B=Bq, H=H, KVH=KVH, D=D, ctx=t + 1, T=T, cache=kind,
+                              single_graph_us=s1, multi_graph_us=sm,
+                              over_single=round(sm['median'] / s1['median'], 3),
+                              over_T_single=round(sm['median'] / (T * s1['median']), 3))), flush=True)
+        del cache
+    # end to end: the 24-layer graph decoder, step_multi(T = 4) next to four step calls
+    import paddle_ray_amd as paddle
+    from paddle_ray_amd.incubate.nn import FusedMultiTransformer, FusedMultiTransformerDecoder
+    paddle.set_device('gpu')
+    E, H, layers, B, ctx, T = 2048, 16, (4 if a.quick else 24), 8, 1024, 4
+    m = FusedMultiTransformer(E, H, 4 * E, num_layers=layers)
+    m.eval()
+    m.to(dtype='bfloat16')
+    d1 = FusedMultiTransformerDecoder(m, B, ctx + 256)
+    dm = FusedMultiTransformerDecoder(m, B, ctx + 256)
+    x = torch.randn(B, T, E, device='cuda', dtype=torch.bfloat16)
+    d1.t.fill_(ctx)
+    dm.t.fill_(ctx)
+
+    def four():
+        for j in range(T):
+            d1.step(x[:, j:j + 1])
+        d1.t.fill_(ctx)  # keep the context length fixed for the measurement
+
+    def multi4():
+        dm.step_multi(x)  # nothing advances without commit
+    s4 = _stats([bench(four, iters=20, warmup=3) for _ in range(samples)], 1e3)
+    sm = _stats([bench(multi4, iters=20, warmup=3) for _ in range(samples)], 1e3)
+    print(json.dumps(dict(model=f'{layers}x{E} FusedMultiTransformerDecoder (HIP graph)', batch=B, ctx=ctx, T=T,
+                          four_steps_ms=s4, step_multi_ms=sm,
+                          step_multi_over_four_steps=round(sm['median'] / s4['median'], 3))), flush=True)
 
 
 if __name__ == '__main__':
