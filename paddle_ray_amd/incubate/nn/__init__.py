@@ -6,3 +6,4 @@ from .layer import (FusedMultiHeadAttention, FusedFeedForward, FusedTransformerE
 from . import attn_bias  # noqa: E402,F401
 from .memory_efficient_attention import memory_efficient_attention  # noqa: E402,F401
 from .loss import identity_loss  # noqa: E402,F401
+from .sampler import TokenSampler  # noqa: E402,F401

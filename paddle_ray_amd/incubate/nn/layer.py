@@ -287,10 +287,14 @@ class FusedMultiTransformerDecoder:
             draft = propose(last, T - 1)             # [B, T - 1] token ids from the draft model
             toks = cat([last, draft], 1)             # [B, T]
             h = dec.step_multi(embed(toks))          # [B, T, E]: row j scores the token after toks[:, j]
-            pred = head(h).argmax(-1)                # [B, T]
+            pred = head(h).argmax(-1)                # [B, T]; or pred = sampler(head(h)), see below
             ok = (pred[:, :-1] == draft).int().cumprod(1).sum(1)   # drafts accepted per slot
             dec.commit(ok + 1)                       # toks[:, :ok + 1] are now part of the sequence
             last = pred.gather(1, ok[:, None])       # the model's own next token
+    With ``sampler = TokenSampler(B, temperature=..., top_k=..., top_p=...)`` (this package) in
+    place of ``argmax``, row j's token is drawn with slot b's temperature / top-k / top-p in one
+    kernel and no host sync (``top_k=1`` is the ``argmax`` above); a draft is then accepted when it
+    equals the token drawn for its row.
     On the GPU T times the query heads per K/V head (T rounded up to a power of two) must not
     exceed 8 (``ops.fused.MULTI_MAX_ROWS``).
     """

@@ -113,6 +113,8 @@ PYBIND11_MODULE(_pra_hip, m) {
   Launch<&pra_mmha_decode_multi>::def(m, "mmha_decode_multi",
                                       "n_tok < 1, more than 8 query rows per K/V row, or anything mmha_decode / "
                                       "mmha_decode_paged refuses");
+  // temperature / top-k / top-p sampling, one id per row (contract above the definition in sample.hip)
+  Launch<&pra_sample_top_p>::def(m, "sample_top_p", "unsupported dtype, R < 0, V < 1 or V > 2^22");
   Launch<&pra_bias_gelu_fwd>::def(m, "bias_gelu_fwd");
   Launch<&pra_bias_gelu_bwd>::def(m, "bias_gelu_bwd");
   Launch<&pra_bias_gelu_bwd_db>::def(m, "bias_gelu_bwd_db");

@@ -3995,3 +3995,209 @@ def gemm_bias_act(x, w, b=None, act=None):
         z = torch.matmul(x, w)
         return _act_ref(z if b is None else z + b, a)
     return GemmBiasActFn.apply(x, w, b, a)
+
+
+# =============================================================================
+# Token sampling: temperature / top-k / top-p (nucleus), one id per row (sample.hip)
+# =============================================================================
+SAMPLE_MAX_V = 1 << 22   # the HIP kernel's vocabulary limit (fixed-point weight sums stay below 2^63)
+_FLT_MAX = float(np.finfo(np.float32).max)
+
+
+def sample_hash_ref(seed, counter, R):
+    """The 32-bit counter hash of (seed, counter, row) for rows 0..R-1 (numpy uint32 [R]): the
+    integer arithmetic of sample.hip ``sample_hash``, built from ``_mix32_t``. For one (seed,
+    counter) it is a bijection of the row index, so no two rows of a launch share a hash."""
+    seed, counter = int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1)
+    a = _mix32_t((seed & _M32) ^ (((seed >> 32) * 0x27d4eb2f) & _M32) ^
+                 (((counter & _M32) * 0x165667b1) & _M32) ^ (((counter >> 32) * 0x85ebca77) & _M32))
+    r = (np.arange(R, dtype=np.uint64) * np.uint64(0xc2b2ae3d)) & np.uint64(_M32)
+    x = np.uint64(a) ^ r
+    x = x ^ (x >> np.uint64(16))
+    x = (x * np.uint64(0x7feb352d)) & np.uint64(_M32)
+    x = x ^ (x >> np.uint64(15))
+    x = (x * np.uint64(0x846ca68b)) & np.uint64(_M32)
+    return (x ^ (x >> np.uint64(16))).astype(np.uint32)
+
+
+def sample_uniform_ref(seed, counter, R):
+    """The uniform each row draws from the hash, ``(h >> 8) * 2^-24`` in [0, 1) (numpy float32
+    [R]); equal bit for bit to what the HIP kernel uses."""
+    return ((sample_hash_ref(seed, counter, R) >> np.uint32(8)).astype(np.float32) *
+            np.float32(2.0 ** -24))
+
+
+def _sample_param(name, v, R, dtype, dev, finite):
+    """One sampling parameter as a contiguous [R] tensor of ``dtype`` on ``dev``. Host values
+    (scalars, lists, numpy arrays, CPU tensors) are validated; a tensor already on the GPU is
+    passed through without a sync (the kernel clamps what it reads)."""
+    v = getattr(v, '_t', v)
+    if isinstance(v, torch.Tensor) and v.is_cuda:
+        t = v.detach().reshape(-1)
+    else:
+        a = np.asarray(v.detach().numpy() if isinstance(v, torch.Tensor) else v)
+        if a.dtype == object or a.dtype.kind not in 'fiub':
+            raise TypeError(f"sample_top_p: {name} must be numeric, got {a.dtype}")
+        a = a.reshape(-1)
+        if finite and not np.isfinite(a.astype(np.float64)).all():
+            raise ValueError(f"sample_top_p: {name} must be finite, got {a.tolist()[:8]}")
+        if dtype == torch.int32:
+            if a.dtype.kind == 'f' and not (a == np.round(a)).all():
+                raise ValueError(f"sample_top_p: {name} must hold integers")
+            a = np.clip(a.astype(np.int64), -(2 ** 31), 2 ** 31 - 1)
+        t = torch.as_tensor(a)
+    if t.numel() not in (1, R):
+        raise ValueError(f"sample_top_p: {name} has {t.numel()} values for {R} rows (a scalar or one per row)")
+    t = t.to(device=dev, dtype=dtype)
+    return (t.expand(R) if t.numel() != R else t).contiguous()
+
+
+def _sample_clamp(t, k, p, V):
+    """The values the kernels use for any parameter bits: NaN / negative temperature -> 0 (greedy),
+    temperature <= FLT_MAX, NaN top_p -> 1, top_k outside [1, V) -> V."""
+    t = torch.where(t > 0, t, torch.zeros_like(t)).clamp(max=_FLT_MAX)
+    p = torch.where(p != p, torch.ones_like(p), p)
+    nk = torch.where((k >= 1) & (k < V), k, torch.full_like(k, V)).long()
+    return t, nk, p
+
+
+def _sample_u24(u):
+    """A uniform as the kernels read it: truncated to 24 bits in [0, 1), NaN -> 0."""
+    k = torch.floor(torch.where(u > 0, u, torch.zeros_like(u)).clamp(max=1.0) * 16777216.0)
+    return k.clamp(max=16777215.0) / 16777216.0
+
+
+@R.register_kernel('sample_top_p', 'ref')
+def _sample_ref(x2, t, k, p, u, probs_mode, seed, offset, step):
+    """The definition in ``sample_top_p`` written with a stable sort, in fp32."""
+    Rn, V = x2.shape
+    dev = x2.device
+    if u is None:
+        counter = int(offset) + (int(step.reshape(-1)[0].item()) if step is not None else 0)
+        u = torch.from_numpy(sample_uniform_ref(seed, counter, Rn)).to(dev)
+    u = _sample_u24(u.float())
+    t, nk, p = _sample_clamp(t.float(), k, p.float(), V)
+    xf = x2.float()
+    xf = torch.where(xf != xf, torch.full_like(xf, float('-inf')), xf) + 0.0        # NaN -> -inf, -0 -> +0
+    vals, order = torch.sort(xf, dim=-1, descending=True, stable=True)              # (x desc, index asc)
+    mx, imax = vals[:, :1], order[:, 0]
+    if probs_mode:
+        w = torch.where(xf == mx, torch.ones_like(xf), xf.clamp(min=0) / mx)
+        empty = ~(mx[:, 0] > 0)
+        cold = torch.zeros_like(empty)
+    else:
+        cold = t == 0
+        w = torch.where(xf == mx, torch.ones_like(xf), torch.exp((xf - mx) / torch.where(cold, 1.0, t)[:, None]))
+        empty = mx[:, 0] == float('-inf')
+    w = torch.where(empty[:, None], torch.zeros_like(w), w)
+    ws = w.gather(1, order)
+    Z = ws.sum(-1)
+    c = ws.cumsum(-1)
+    n_p = ((c < (p * Z)[:, None]).sum(-1) + 1).clamp(max=V)
+    n_p = torch.where(p >= 1, torch.full_like(n_p, V), n_p)
+    n = torch.minimum(n_p, nk).clamp(min=1)
+    keep_sorted = torch.arange(V, device=dev)[None, :] < n[:, None]
+    kept = torch.zeros_like(keep_sorted).scatter(1, order, keep_sorted)
+    wk = torch.where(kept, w, torch.zeros_like(w))
+    M = (ws * keep_sorted).sum(-1)
+    hit = kept & (wk.cumsum(-1) > (u * M)[:, None])
+    first = hit.to(torch.int8).argmax(-1)                                            # first True
+    last = V - 1 - kept.flip(-1).to(torch.int8).argmax(-1)
+    ids = torch.where(hit.any(-1), first, last)
+    greedy = cold | (k == 1) | ~(p > 0) | empty
+    ids = torch.where(greedy, imax, ids)
+    prob = w.gather(1, ids[:, None])[:, 0] / Z
+    prob = torch.where(cold, torch.ones_like(prob), prob)
+    prob = torch.where(empty, torch.zeros_like(prob), prob)
+    return ids, prob
+
+
+@R.register_kernel('sample_top_p', 'hip', dtypes=_FLOATS)
+def _sample_hip(x2, t, k, p, u, probs_mode, seed, offset, step, u_out=None):
+    Rn, V = x2.shape
+    ids = torch.empty(Rn, device=x2.device, dtype=torch.int64)
+    prob = torch.empty(Rn, device=x2.device, dtype=torch.float32)
+    _native.lib().sample_top_p(_ptr(x2), _ptr(t), _ptr(k), _ptr(p), _ptr(u), _ptr(ids), _ptr(prob), _ptr(u_out),
+                               Rn, V, _dt(x2), int(bool(probs_mode)), int(seed) & (2 ** 64 - 1),
+                               int(offset) & (2 ** 64 - 1), _ptr(step), _stream())
+    return ids, prob
+
+
+def sample_top_p(x, temperature=1.0, top_k=0, top_p=1.0, seed=0, offset=0, step=None, uniform=None,
+                 probs=False):
+    """Pick one token id per row of ``x`` [..., V] (fp32 / f16 / bf16 logits, or probabilities with
+    ``probs=True``) -> ``(ids int64 [...], probs fp32 [...])``. Leading dimensions are rows; every
+    row r has its own ``temperature[r]`` (fp32), ``top_k[r]`` (int32) and ``top_p[r]`` (fp32),
+    given as scalars or one value per row (lists, numpy arrays, tensors). For one row:
+
+    - a NaN entry counts as -inf (and -0 as +0);
+    - greedy: ``temperature <= 0``, ``top_k == 1`` or ``top_p <= 0`` give the lowest index of the
+      row maximum;
+    - weights ``w_i = exp((x_i - max) / temperature)`` (exactly 1 at the maximum), ``Z = sum w``;
+      with ``probs=True`` ``w_i = max(x_i, 0) / max`` and the temperature is ignored;
+    - order: entries ranked by (x descending, index ascending);
+    - ``n_p``: the shortest prefix of that order whose weight is >= ``top_p * Z`` (V if
+      ``top_p >= 1`` or the sum never gets there); ``n_k = top_k`` if ``1 <= top_k < V`` else V;
+      the first ``n = max(1, min(n_p, n_k))`` entries are kept, so a tie group cut by ``n`` keeps
+      its lowest indices;
+    - draw: with M the kept weight, the kept entries are walked in ascending index order and the
+      result is the first index whose running kept weight exceeds ``u * M`` (the last kept index
+      if rounding leaves none), ``u`` in [0, 1) being one uniform per row;
+    - ``probs[r] = w_id / Z``, the chosen token's probability under the full softmax, not
+      renormalised to the kept set (1 for ``temperature <= 0``);
+    - a row with no weight (no entry above -inf; ``probs=True``: none above 0) gives its argmax,
+      which is id 0 for a row of -inf / NaN, with prob 0.
+
+    ``u`` is ``uniform[r]`` when a [R] tensor is given, truncated to 24 bits; otherwise
+    ``(h >> 8) * 2^-24`` with h the counter hash of ``(seed, offset + step, r)``
+    (``sample_uniform_ref``), ``step`` being an optional device int64 counter that a captured
+    graph advances so that replays draw new numbers. Host parameter values must be finite; GPU
+    tensors are not read on the host, and the kernel clamps whatever they hold (NaN temperature ->
+    greedy, NaN top_p -> 1, top_k outside [1, V) -> V), so every id is in [0, V). A host
+    parameter (scalar, list, numpy array, CPU tensor) is expanded to [R] and copied to x's device
+    on every call, one host-to-device copy per parameter, which a graph capture does not allow:
+    to capture the op, or to spare the copies, pass [R] tensors that already live on the device
+    (``TokenSampler`` keeps such buffers).
+
+    ``'ref'`` is this definition in fp32 PyTorch with a sort (CPU, and the tests' reference);
+    ``'hip'`` is one launch of sample.hip, no sort, bitwise reproducible, V <= ``SAMPLE_MAX_V``
+    (a larger V raises ValueError)."""
+    x = getattr(x, '_t', x)
+    if x.dim() < 1 or x.shape[-1] < 1:
+        raise ValueError(f"sample_top_p: x must be [..., V] with V >= 1, got {tuple(x.shape)}")
+    if not x.is_floating_point():
+        raise TypeError(f"sample_top_p: x must be floating point, got {x.dtype}")
+    lead, V = x.shape[:-1], x.shape[-1]
+    if V >= 2 ** 31:
+        raise ValueError(f"sample_top_p: V = {V} does not fit int32")
+    x2 = x.detach().reshape(-1, V)
+    x2 = x2 if x2.is_contiguous() else x2.contiguous()
+    Rn, dev = x2.shape[0], x2.device
+    t = _sample_param('temperature', temperature, Rn, torch.float32, dev, True)
+    k = _sample_param('top_k', top_k, Rn, torch.int32, dev, False)
+    p = _sample_param('top_p', top_p, Rn, torch.float32, dev, True)
+    u = None
+    if uniform is not None:
+        u = getattr(uniform, '_t', uniform)
+        if not isinstance(u, torch.Tensor) or u.numel() != Rn:
+            raise ValueError(f"sample_top_p: uniform must be a tensor of {Rn} values (one per row)")
+        u = u.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+    if step is not None:
+        step = getattr(step, '_t', step)
+        if not isinstance(step, torch.Tensor) or step.dtype != torch.int64 or step.numel() != 1 or \
+                step.device != dev:
+            raise ValueError("sample_top_p: step must be a one-element int64 tensor on x's device")
+    ids, prob = R.dispatch('sample_top_p', x2, x2, t, k, p, u, bool(probs), int(seed), int(offset), step)
+    return ids.reshape(lead), prob.reshape(lead)
+
+
+def sample_uniform_hip(seed, counter, R, device, step=None):
+    """For tests only, not part of the sampling interface: the uniforms the HIP kernel draws for
+    rows 0..R-1 at ``counter`` (+ ``step``), fp32 [R], read back through the entry's debug output
+    ``u_out`` from a launch over one-entry rows and compared with ``sample_uniform_ref``."""
+    x = torch.zeros(R, 1, device=device, dtype=torch.float32)
+    t = torch.ones(R, device=device, dtype=torch.float32)
+    k = torch.zeros(R, device=device, dtype=torch.int32)
+    out = torch.empty(R, device=device, dtype=torch.float32)
+    _sample_hip(x, t, k, t, None, False, seed, counter, step, u_out=out)
+    return out

@@ -119,6 +119,26 @@ def multinomial(x, num_samples=1, replacement=False, name=None):
     return Tensor(torch.multinomial(_u(x), num_samples, replacement))
 
 
+def top_p_sampling(x, ps, threshold=None, seed=None, name=None):
+    """Nucleus sampling over probabilities (parity: paddle.tensor.top_p_sampling). ``x`` [B, V]
+    holds each row's probabilities, ``ps`` [B] or [B, 1] its top-p; returns ``(out [B, 1], the
+    sampled entries of x in x's dtype, ids [B, 1] int64)``. One fused kernel on the GPU
+    (``ops.fused.sample_top_p`` with ``probs=True``, which states the kept set and the draw).
+    ``seed=None`` or ``-1`` draws the seed from the host generator, so ``paddle.seed`` makes the
+    ids reproducible; ``threshold`` (a per-row probability floor) is not implemented."""
+    from ..ops.fused import sample_top_p, _dropout_seed
+    if threshold is not None:
+        raise NotImplementedError("top_p_sampling: threshold= (a per-row probability floor) is not "
+                                  "implemented; pass threshold=None")
+    xt = _u(x)
+    if xt.dim() != 2:
+        raise ValueError(f"top_p_sampling: x must be [batch, vocab], got {tuple(xt.shape)}")
+    s = _dropout_seed() if seed is None or int(seed) == -1 else int(seed)
+    ids, _ = sample_top_p(xt, top_p=_u(ps), seed=s, probs=True)
+    ids = ids[:, None]
+    return Tensor(xt.detach().gather(1, ids)), Tensor(ids)
+
+
 def exponential_(x, lam=1.0, name=None):
     with torch.no_grad():
         x._t.exponential_(lam)
