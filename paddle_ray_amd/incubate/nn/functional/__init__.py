@@ -240,7 +240,9 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
                             cache_k_quant_scales=None, cache_v_quant_scales=None,
                             cache_k_dequant_scales=None, cache_v_dequant_scales=None,
                             quant_round_type=1, quant_max_bound=127.0, quant_min_bound=-127.0,
-                            block_tables=None):
+                            block_tables=None, qkv_weight_scales=None, linear_weight_scales=None,
+                            ffn1_weight_scales=None, ffn2_weight_scales=None, weight_dtype=None,
+                            weight_group_size=-1):
     """N transformer layers for inference / generation (parity: reference
     incubate/nn/functional/fused_transformer.py:872 and fused_multi_transformer_op.cu.h).
 
@@ -283,6 +285,17 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
       through the table, one indexed scatter per plane; a position whose entry is outside
       [0, NB) is not written, and its own attention is unchanged. The pool is not indexed by
       batch, so a call may carry any subset of the sequences with their table rows.
+    * weight-only int8 / int4 products: with ``qkv_weight_scales`` / ``linear_weight_scales`` /
+      ``ffn1_weight_scales`` / ``ffn2_weight_scales`` (per-layer lists of fp32 scales) the matching
+      weight list holds the ``qweight`` tensors of ``paddle.nn.quant.weight_quantize`` with
+      ``weight_dtype`` ('int8' / 'int4') and ``weight_group_size``, each quantised from the
+      ``[K, N]`` orientation of its product (a ``trans_qkvw=True`` qkv weight: the reshaped
+      transpose ``[E, 3*H*D]``); the head dim of a quantised qkv weight is taken from the cache or
+      the qkv bias. A decode step of at most ``ops.fused.WO_MAX_ROWS`` rows runs all four products
+      on the weight-only HIP kernel (``ops.fused.weight_only_linear``): the qkv bias and FFN1's
+      bias + activation in its epilogue, the out-projection and FFN2 without bias (the following
+      add_dropout_layer_norm adds theirs). The context phase and taller steps dequantise each
+      weight to the model dtype, layer by layer, and run the floating-point path unchanged.
     * every residual add + dropout + following LayerNorm is ONE add_dropout_layer_norm
       kernel; FFN1 runs with its bias+activation in the GEMM epilogue.
     Returns ``out`` or ``(out, cache_kvs)`` when caches are given (updated in place)."""
@@ -314,6 +327,21 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
     sl = _t(seq_lens)
     zero_b = torch.zeros(E, dtype=h.dtype, device=h.device)
     one_w = torch.ones(E, dtype=h.dtype, device=h.device)
+    wo_lists = (qkv_weight_scales, linear_weight_scales, ffn1_weight_scales, ffn2_weight_scales)
+    if any(s is not None for s in wo_lists) and weight_dtype not in ('int8', 'int4'):
+        raise ValueError(f"fused_multi_transformer: weight scales need weight_dtype 'int8' or 'int4', "
+                         f"got {weight_dtype!r}")
+    wo_kernel = decode and B * S <= K.WO_MAX_ROWS      # else: dequantise, then the float path
+    wo_act = 'gelu' if activation == 'gelu' else activation
+
+    def wo_scale(lst, i):
+        return _t(lst[i]) if lst is not None and lst[i] is not None else None
+
+    def wo_linear(v, w, sc, bias=None, act=None):
+        return K.weight_only_linear(v, w, sc, bias, act, weight_dtype, weight_group_size)
+
+    def wo_float(w, sc):
+        return K.weight_dequantize(w, sc, weight_dtype, weight_group_size, h.dtype)
 
     def lnp(lst, i, default):
         return _u(lst[i]) if lst is not None and lst[i] is not None else default
@@ -323,8 +351,26 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
         if pre_layer_norm else h
     for i in range(n):
         qb = _t(qkv_biases[i]) if qkv_biases else None
+        wq, tq, sq = _u(qkv_weights[i]), trans_qkvw, wo_scale(qkv_weight_scales, i)
+        if sq is not None:                           # qweight [3*H*D (or (H + 2*KVH)*D), E]
+            if cache_kvs is not None:
+                D = _u(cache_kvs[i]).shape[-1]
+            elif qb is not None:
+                D = qb.shape[-1]
+            else:
+                raise ValueError("fused_multi_transformer: a weight-only qkv weight needs cache_kvs or "
+                                 "qkv_biases to give the head dim")
+            if not wo_kernel:
+                wq, tq = wo_float(wq, sq), False
+                wq = wq.view(E, -1, D) if KVH else wq.view(E, 3, -1, D)
+        if sq is not None and wo_kernel:
+            qkv = wo_linear(y, wq, sq, None if qb is None else qb.reshape(-1))
+            qkv = qkv.view(B, S, -1, D) if KVH else qkv.view(B, S, 3, -1, D)
+        elif KVH:
+            qkv = _qkv_rows(y, wq, qb, tq)           # [B, S, H + 2*KVH, D]
+        else:
+            qkv = _qkv(y, wq, qb, tq)
         if KVH:
-            qkv = _qkv_rows(y, _u(qkv_weights[i]), qb, trans_qkvw)   # [B, S, H + 2*KVH, D]
             H, D = qkv.shape[2] - 2 * KVH, qkv.shape[3]
             if H <= 0 or H % KVH != 0:
                 raise ValueError(f"fused_multi_transformer: qkv weight {i} has {qkv.shape[2]} head "
@@ -334,7 +380,6 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
                 qk = _rotary(qkv[:, :, :H + KVH], rot[0], rot[1], rotary_emb_dims)
                 qkv = torch.cat([qk, qkv[:, :, H + KVH:]], 2)
         else:
-            qkv = _qkv(y, _u(qkv_weights[i]), qb, trans_qkvw)
             H, D = qkv.shape[3], qkv.shape[4]
             if rot is not None:
                 q = _rotary(qkv[:, :, 0], rot[0], rot[1], rotary_emb_dims)
@@ -417,7 +462,13 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
                     None if am is None else am.to(q.dtype), p)
                 o = o.transpose(1, 2)
             o = o.reshape(B, S, H * D)
-        a = K.linear(o, _u(linear_weights[i]))
+        sl_ = wo_scale(linear_weight_scales, i)
+        if sl_ is None:
+            a = K.linear(o, _u(linear_weights[i]))
+        elif wo_kernel:
+            a = wo_linear(o, _u(linear_weights[i]), sl_)
+        else:
+            a = K.linear(o, wo_float(_u(linear_weights[i]), sl_))
         lb = _t(linear_biases[i]) if linear_biases else None
         lb = zero_b if lb is None else lb
         if pre_layer_norm:
@@ -428,8 +479,12 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
                                             lnp(ln_biases, i, zero_b), p, epsilon, training)
             y = r
         b1 = _t(ffn1_biases[i]) if ffn1_biases else None
-        w1 = _u(ffn1_weights[i])
-        if decode and y.is_cuda:
+        w1, s1 = _u(ffn1_weights[i]), wo_scale(ffn1_weight_scales, i)
+        if s1 is not None and not wo_kernel:
+            w1, s1 = wo_float(w1, s1), None
+        if s1 is not None:
+            f = wo_linear(y, w1, s1, b1, wo_act)
+        elif decode and y.is_cuda:
             # skinny decode rows: hipBLASLt + the activation (3.0 vs 3.6 ms per 24-layer graph
             # decode step at batch 8); the 256-row MFMA tile would idle
             f = y.reshape(-1, E) @ w1 if b1 is None else torch.addmm(b1, y.reshape(-1, E), w1)
@@ -439,7 +494,13 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
             f = K.gemm_bias_act(y, w1, b1, 'gelu' if activation == 'gelu' else activation)
         if p:
             f = torch.nn.functional.dropout(f, p, True)
-        f = K.linear(f, _u(ffn2_weights[i]))
+        s2 = wo_scale(ffn2_weight_scales, i)
+        if s2 is None:
+            f = K.linear(f, _u(ffn2_weights[i]))
+        elif wo_kernel:
+            f = wo_linear(f, _u(ffn2_weights[i]), s2)
+        else:
+            f = K.linear(f, wo_float(_u(ffn2_weights[i]), s2))
         b2 = _t(ffn2_biases[i]) if ffn2_biases else None
         b2 = zero_b if b2 is None else b2
         if pre_layer_norm:

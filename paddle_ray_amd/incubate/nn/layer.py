@@ -297,12 +297,41 @@ class FusedMultiTransformerDecoder:
     equals the token drawn for its row.
     On the GPU T times the query heads per K/V head (T rounded up to a power of two) must not
     exceed 8 (``ops.fused.MULTI_MAX_ROWS``).
+
+    Weight-only int8 / int4: ``weight_only='int8'`` or ``'int4'`` (``weight_group_size`` -1 for one
+    scale per output channel, or 64 / 128) quantises the model's qkv, out-projection, FFN1 and FFN2
+    weights once, here (``paddle.nn.quant.weight_quantize`` of each product's ``[K, N]``
+    orientation; kept in ``self.wo_weights``), and never reads the floating weights again: half or
+    a quarter of the bytes a decode step streams and of the memory the weights occupy. ``step`` and
+    ``step_multi`` run the four products on the weight-only HIP kernel inside the captured graphs
+    (``ops.fused.weight_only_linear``, at most ``ops.fused.WO_MAX_ROWS`` = B * T rows); ``prefill``
+    and ``admit`` dequantise each weight per layer and run the floating-point path. Only the linear
+    products differ: every mode above composes with it.
     """
 
     def __init__(self, model, batch_size, max_seq_len, use_graph=True, kv_cache_dtype=None,
-                 cache_scales=None, block_size=None, num_blocks=None):
+                 cache_scales=None, block_size=None, num_blocks=None, weight_only=None,
+                 weight_group_size=-1):
         import torch
         self.model = model
+        if weight_only not in (None, 'int8', 'int4'):
+            raise ValueError(f"FusedMultiTransformerDecoder: weight_only must be None, 'int8' or 'int4', "
+                             f"got {weight_only!r}")
+        self.weight_only, self.wo_weights = weight_only, None
+        if weight_only is not None:
+            from ...ops import fused as K
+            E = model.embed_dim
+            self.wo_weights = {}
+            for name in ('qkv', 'linear', 'ffn1', 'ffn2'):
+                pairs = []
+                for p in getattr(model, name + '_weights'):
+                    w = p._t.detach()
+                    if name == 'qkv':            # the [E, N] orientation of the product
+                        w = w.reshape(-1, E).t() if model._trans_qkvw else w.reshape(E, -1)
+                    pairs.append(K.weight_quantize(w, weight_only, weight_group_size))
+                self.wo_weights[name + '_weights'] = [q for q, _ in pairs]
+                self.wo_weights[name + '_weight_scales'] = [s for _, s in pairs]
+            self.wo_weights.update(weight_dtype=weight_only, weight_group_size=int(weight_group_size))
         self.B, self.L = int(batch_size), int(max_seq_len)
         p0 = model.qkv_weights[0]._t
         self.dev, self.dtype = p0.device, p0.dtype
@@ -376,6 +405,21 @@ class FusedMultiTransformerDecoder:
         from ...framework.core import Tensor
         return [Tensor(c) for c in self.caches]
 
+    def _model(self, x, caches, **kw):
+        """``self.model(x, caches=caches, **kw)``, or with ``weight_only`` the same layers over the
+        quantised weights (the model supplies the norms, the biases and its settings)."""
+        m = self.model
+        if self.wo_weights is None:
+            return m(x, caches=caches, **kw)
+        wo = self.wo_weights
+        return FF.fused_multi_transformer(
+            x, m.ln_scales, m.ln_biases, wo['qkv_weights'], m.qkv_biases, wo['linear_weights'],
+            m.linear_biases, m.ffn_ln_scales, m.ffn_ln_biases, wo['ffn1_weights'], m.ffn1_biases,
+            wo['ffn2_weights'], m.ffn2_biases, pre_layer_norm=m.normalize_before, epsilon=m._epsilon,
+            cache_kvs=caches, dropout_rate=m.dropout_rate, activation=m.activation, training=m.training,
+            trans_qkvw=m._trans_qkvw, gqa_group_size=m._gqa_group_size,
+            **{k: v for k, v in wo.items() if not k.endswith('_weights')}, **kw)
+
     def set_mask(self, attn_mask):
         import torch
         m = attn_mask._t if hasattr(attn_mask, '_t') else torch.as_tensor(attn_mask)
@@ -422,12 +466,12 @@ class FusedMultiTransformerDecoder:
                 KVH, D = self.caches[0].shape[2], self.caches[0].shape[4]
                 tmp = [torch.zeros(2, self.B, KVH, S0, D, device=self.dev, dtype=self.dtype)
                        for _ in self.caches]
-                out, _ = self.model(Tensor(xt), attn_mask=attn_mask, caches=[Tensor(c) for c in tmp],
-                                    **{k: v for k, v in kw.items() if k != 'block_tables'})
+                out, _ = self._model(Tensor(xt), [Tensor(c) for c in tmp], attn_mask=attn_mask,
+                                     **{k: v for k, v in kw.items() if k != 'block_tables'})
                 self._quantize_prompt(tmp, sl if ragged else None)
             else:
-                out, _ = self.model(Tensor(xt), attn_mask=attn_mask, caches=self._caches(), **kw,
-                                    **self._qkw)
+                out, _ = self._model(Tensor(xt), self._caches(), attn_mask=attn_mask, **kw,
+                                     **self._qkw)
         if ragged:
             self.lens.copy_(sl)
             self.t.copy_(sl.max().reshape(1))
@@ -544,12 +588,12 @@ class FusedMultiTransformerDecoder:
             if self.dynamic_scales:
                 KVH, D = self.caches[0].shape[2], self.caches[0].shape[4]
                 tmp = [torch.zeros(2, 1, KVH, S, D, device=self.dev, dtype=self.dtype) for _ in self.caches]
-                out = self.model(Tensor(xt), attn_mask=attn_mask, caches=[Tensor(c) for c in tmp],
-                                 **{k: v for k, v in kw.items() if k != 'block_tables'})[0]
+                out = self._model(Tensor(xt), [Tensor(c) for c in tmp], attn_mask=attn_mask,
+                                  **{k: v for k, v in kw.items() if k != 'block_tables'})[0]
                 self._quantize_prompt(tmp, None, slot=b)
             else:
-                out, _ = self.model(Tensor(xt), attn_mask=attn_mask, caches=self._caches(), **kw,
-                                    **self._qkw)
+                out, _ = self._model(Tensor(xt), self._caches(), attn_mask=attn_mask, **kw,
+                                     **self._qkw)
         self.lens[b].fill_(S)
         self.t.copy_(torch.clamp(self.t, min=S))
         self._pos[b] = S
@@ -598,8 +642,8 @@ class FusedMultiTransformerDecoder:
             r = self.rot.index_select(1, pos)
             r = r.expand(2, self.B, r.shape[-1])
             kw.update(rotary_embs=Tensor(r[:, :, None, None]), rotary_emb_dims=self.rot_dims)
-        out, _ = self.model(Tensor(self.x_buf), attn_mask=Tensor(self.mask), caches=self._caches(),
-                            time_step=Tensor(self.t), **kw)
+        out, _ = self._model(Tensor(self.x_buf), self._caches(), attn_mask=Tensor(self.mask),
+                             time_step=Tensor(self.t), **kw)
         return out._t
 
     def _step_multi_eager(self, T):
@@ -616,8 +660,8 @@ class FusedMultiTransformerDecoder:
                    ).clamp(max=self.L - 1)
             r = self.rot.index_select(1, pos.reshape(-1)).view(2, self.B, 1, T, -1)
             kw.update(rotary_embs=Tensor(r), rotary_emb_dims=self.rot_dims)
-        out, _ = self.model(Tensor(self._multi[T][0]), attn_mask=Tensor(self.mask), caches=self._caches(),
-                            time_step=Tensor(self.t), **kw)
+        out, _ = self._model(Tensor(self._multi[T][0]), self._caches(), attn_mask=Tensor(self.mask),
+                             time_step=Tensor(self.t), **kw)
         return out._t
 
     def step_multi(self, x):

@@ -11,6 +11,7 @@ from .format import (LinearQuanter, LinearDequanter, LinearQuanterDequanter,  # 
                      ConvertibleQuantedLayer)
 from .stub import Stub, QuanterStub  # noqa: F401
 from .lsq import FakeQuantActLSQPlus, FakeQuantWeightLSQPlus  # noqa: F401
+from .quantized_linear import weight_quantize, weight_dequantize, weight_only_linear  # noqa: F401
 from . import qat  # noqa: F401
 
 __all__ = ['Stub']

@@ -82,6 +82,9 @@ def _stamp_path():
 
 
 _HIP_FLAGS = ('-O3', '-fPIC', '-std=c++17', '-munsafe-fp-atomics')
+# per-source additions (part of that object's rebuild key only). wo_gemm.hip scales fp32 vectors:
+# keep the compiler from pairing those into packed fp32 instructions.
+_EXTRA_FLAGS = {'wo_gemm.hip': ('-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops')}
 
 
 def _toolchain_key():
@@ -134,7 +137,8 @@ def build(force=False, verbose=True):
         src = os.path.join(CSRC, f)
         obj = os.path.join(BUILD, f.replace('.hip', '.o'))
         objs.append(obj)
-        cmd = [HIPCC, f'--offload-arch={ARCH}', *_HIP_FLAGS, '-c', src, '-o', obj, '-I', CSRC]
+        cmd = [HIPCC, f'--offload-arch={ARCH}', *_HIP_FLAGS, *_EXTRA_FLAGS.get(f, ()), '-c', src, '-o', obj,
+               '-I', CSRC]
         keys[os.path.basename(obj)] = _digest([src] + _header_closure(src), cmd + [_hipcc_version()])
         if force or _needs(obj, keys[os.path.basename(obj)], manifest):
             jobs.append(cmd)

@@ -67,6 +67,7 @@ PYBIND11_MODULE(_pra_hip, m) {
   m.def("gemm_get_pts", &pra_gemm_get_pts);
   m.def("gemm_get_w4", &pra_gemm_get_w4);
   m.def("mmha_splits", &pra_mmha_splits);
+  m.def("wo_gemm_splits", &pra_wo_gemm_splits);
   m.def("adl_supported", &pra_adl_supported);
   m.def("bn_nrb", &pra_bn_nrb);
   m.def("build_info", []() { return std::string(pra_build_info()); });
@@ -115,6 +116,10 @@ PYBIND11_MODULE(_pra_hip, m) {
                                       "mmha_decode_paged refuses");
   // temperature / top-k / top-p sampling, one id per row (contract above the definition in sample.hip)
   Launch<&pra_sample_top_p>::def(m, "sample_top_p", "unsupported dtype, R < 0, V < 1 or V > 2^22");
+  // weight-only int8 / int4 linear for at most 64 rows (contract above the definition in wo_gemm.hip)
+  Launch<&pra_wo_gemm>::def(m, "wo_gemm",
+                            "M outside [1, 64], N % 16, K % 64, K % group_size, or an unsupported group size / "
+                            "activation / dtype / split count");
   Launch<&pra_bias_gelu_fwd>::def(m, "bias_gelu_fwd");
   Launch<&pra_bias_gelu_bwd>::def(m, "bias_gelu_bwd");
   Launch<&pra_bias_gelu_bwd_db>::def(m, "bias_gelu_bwd_db");

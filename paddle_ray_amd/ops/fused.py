@@ -4201,3 +4201,199 @@ def sample_uniform_hip(seed, counter, R, device, step=None):
     out = torch.empty(R, device=device, dtype=torch.float32)
     _sample_hip(x, t, k, t, None, False, seed, counter, step, u_out=out)
     return out
+
+
+# =============================================================================
+# Weight-only int8 / int4 linear for decode steps (wo_gemm.hip). Parity: the reference's
+# python/paddle/nn/quant/quantized_linear.py weight_quantize / weight_dequantize / weight_only_linear.
+# =============================================================================
+WO_MAX_ROWS = 64         # rows of x the HIP kernel takes; taller products run the ref kernel
+_WO_ALGO = {'weight_only_int8': ('int8', 127.0), 'weight_only_int4': ('int4', 7.0),
+            'int8': ('int8', 127.0), 'int4': ('int4', 7.0)}
+
+
+def _wo_algo(algo):
+    if algo not in _WO_ALGO:
+        raise ValueError(f"weight-only quantisation: algo / weight_dtype must be one of {sorted(_WO_ALGO)}, "
+                         f"got {algo!r}")
+    return _WO_ALGO[algo]
+
+
+def _wo_group(K, group_size, wdt):
+    g = int(group_size)
+    if g not in (-1, 64, 128):
+        raise ValueError(f"weight-only quantisation: group_size must be -1, 64 or 128, got {group_size}")
+    if g > 0 and K % g:
+        raise ValueError(f"weight-only quantisation: K = {K} is not a multiple of group_size = {g}")
+    if wdt == 'int4' and K % 2:
+        raise ValueError(f"weight-only quantisation: int4 packs two levels per byte, K = {K} is odd")
+    return g
+
+
+def _wo_tiled(K, N):
+    """Whether [K, N] levels are stored in the kernel's tile order (else plain [N, K] rows)."""
+    return K % 64 == 0 and N % 16 == 0
+
+
+def _wo_pack(lv, wdt):
+    """Integer levels [K, N] -> the byte image [N, K] (int8) / [N, K // 2] (int4) of wo_gemm.hip:
+    16-channel tiles, 64-k chunks, a lane's 16 bytes being the MFMA operands of its channel."""
+    K, N = lv.shape
+    lt = lv.t().contiguous()
+    tiled = _wo_tiled(K, N)
+    if wdt == 'int8':
+        if tiled:                                  # [nt, ch, c, s, q, i] -> [nt, c, q, ch, s, i]
+            lt = lt.view(N // 16, 16, K // 64, 2, 4, 8).permute(0, 2, 4, 1, 3, 5)
+        return lt.reshape(N, K).to(torch.int8).contiguous()
+    nib = lt + 8
+    if tiled:
+        S = K // 128
+        parts = []
+        if S:                                      # [nt, ch, sc, s, q, i] -> [nt, sc, q, ch, s, i]
+            parts.append(nib[:, :S * 128].reshape(N // 16, 16, S, 4, 4, 8).permute(0, 2, 4, 1, 3, 5)
+                         .reshape(N // 16, -1))
+        if K % 128:                                # the last 64 k: [nt, ch, s, q, i] -> [nt, q, ch, s, i]
+            parts.append(nib[:, S * 128:].reshape(N // 16, 16, 2, 4, 8).permute(0, 3, 1, 2, 4)
+                         .reshape(N // 16, -1))
+        nib = torch.cat(parts, 1)
+    nib = nib.reshape(N, K // 2, 2).to(torch.uint8)
+    return (nib[..., 0] | (nib[..., 1] << 4)).view(torch.int8).contiguous()
+
+
+def _wo_unpack(qweight, K, N, wdt):
+    """The inverse of ``_wo_pack``: integer levels [K, N] (int16)."""
+    tiled = _wo_tiled(K, N)
+    if wdt == 'int8':
+        lt = qweight.to(torch.int16)
+        if tiled:
+            lt = lt.view(N // 16, K // 64, 4, 16, 2, 8).permute(0, 3, 1, 4, 2, 5)
+        return lt.reshape(N, K).t().contiguous()
+    b = qweight.view(torch.uint8).to(torch.int16)
+    nib = torch.stack([b & 15, b >> 4], -1).reshape(N, K)
+    if tiled:
+        nib = nib.reshape(N // 16, 16 * K)
+        S = K // 128
+        parts = []
+        if S:
+            parts.append(nib[:, :S * 2048].reshape(N // 16, S, 4, 16, 4, 8).permute(0, 3, 1, 4, 2, 5)
+                         .reshape(N // 16, 16, S * 128))
+        if K % 128:
+            parts.append(nib[:, S * 2048:].reshape(N // 16, 4, 16, 2, 8).permute(0, 2, 3, 1, 4)
+                         .reshape(N // 16, 16, 64))
+        nib = torch.cat(parts, 2)
+    return (nib.reshape(N, K) - 8).t().contiguous()
+
+
+def weight_quantize(w, algo='weight_only_int8', group_size=-1):
+    """Quantise a ``[K, N]`` floating-point weight for ``weight_only_linear``: returns
+    ``(qweight, scale)``. ``scale`` (fp32, ``[N]``, or ``[K / group_size, N]`` for ``group_size``
+    64 / 128) is ``absmax / 127`` (int8) or ``absmax / 7`` (int4) over the channel or the group,
+    and 1 where that is all zero; ``level = clamp(round_half_even(w_f32 / scale))``.
+    ``qweight`` is ``torch.int8``, ``[N, K]`` (int8) or ``[N, K // 2]`` (int4, two levels per
+    byte), with its bytes in the tile order of the HIP kernel (``ops/csrc/wo_gemm.hip``): it is not
+    a matrix to index (a shape the kernel does not take, K % 64 or N % 16, keeps plain [N, K]
+    rows). The only supported readers are ``weight_dequantize`` and
+    ``weight_only_linear``, called with the same ``algo`` and ``group_size``."""
+    w = getattr(w, '_t', w)
+    wdt, qmax = _wo_algo(algo)
+    if w.dim() != 2 or not w.is_floating_point():
+        raise ValueError(f"weight_quantize: w must be a floating-point [K, N] matrix, got {w.dtype} "
+                         f"{tuple(w.shape)}")
+    K, N = w.shape
+    g = _wo_group(K, group_size, wdt)
+    wf = w.detach().float()
+    wg = wf.reshape(K // g, g, N) if g > 0 else wf.reshape(1, K, N)
+    amax = wg.abs().amax(1)
+    scale = torch.where(amax > 0, amax / qmax, torch.ones_like(amax))            # [K / g, N]
+    # the quotient in float64: an fp32 division can round 35.4999998 up to the tie 35.5 and
+    # past it, which would leave the level more than scale / 2 from the weight
+    lv = torch.round(wg.double() / scale.double()[:, None]).clamp_(-qmax, qmax).reshape(K, N).to(torch.int16)
+    return _wo_pack(lv, wdt), (scale if g > 0 else scale[0]).contiguous()
+
+
+def _wo_check(qweight, scale, wdt, group_size, K=None):
+    """Shapes of a (qweight, scale) pair -> (K, N, group_size); ValueError with the shapes."""
+    if not isinstance(qweight, torch.Tensor) or qweight.dtype != torch.int8 or qweight.dim() != 2:
+        raise ValueError(f"weight-only: the weight must be the int8 tensor weight_quantize returned, got "
+                         f"{getattr(qweight, 'dtype', type(qweight))} {tuple(getattr(qweight, 'shape', ()))}")
+    N = qweight.shape[0]
+    Kq = qweight.shape[1] * (2 if wdt == 'int4' else 1)
+    if K is not None and K != Kq:
+        raise ValueError(f"weight-only: x has K = {K}, the {wdt} weight {tuple(qweight.shape)} holds K = {Kq}")
+    g = _wo_group(Kq, group_size, wdt)
+    want = (Kq // g, N) if g > 0 else (N,)
+    if scale is None or tuple(scale.shape) != want or scale.dtype != torch.float32:
+        raise ValueError(f"weight-only: scale must be fp32 {want} for a {wdt} weight {tuple(qweight.shape)} "
+                         f"(N = {N}, K = {Kq}, group_size = {g}), got "
+                         f"{None if scale is None else (scale.dtype, tuple(scale.shape))}")
+    return Kq, N, g
+
+
+def weight_dequantize(qweight, scale, algo='weight_only_int8', group_size=-1, out_dtype=torch.float16):
+    """``[K, N]`` = level * scale of a ``weight_quantize`` pair, computed in fp32 and cast to
+    ``out_dtype``; with ``torch.float32`` it is the exact inverse of the layout."""
+    qweight, scale = getattr(qweight, '_t', qweight), getattr(scale, '_t', scale)
+    wdt, _ = _wo_algo(algo)
+    K, N, g = _wo_check(qweight, scale, wdt, group_size)
+    lv = _wo_unpack(qweight, K, N, wdt).float()
+    w = (lv.view(K // g, g, N) * scale[:, None]).view(K, N) if g > 0 else lv * scale
+    return w.to(out_dtype)
+
+
+@R.register_kernel('weight_only_linear', 'ref')
+def _wo_ref(x2, qweight, scale, bias, act, wdt, g, splits=None):
+    """Dequantise, then the library product in fp32."""
+    z = x2.float() @ weight_dequantize(qweight, scale, wdt, g, torch.float32)
+    if bias is not None:
+        z = z + bias.float()
+    return _act_ref(z, act).to(x2.dtype)
+
+
+@R.register_kernel('weight_only_linear', 'hip', dtypes=_HALF)
+def _wo_hip(x2, qweight, scale, bias, act, wdt, g, splits=None):
+    M, K = x2.shape
+    N = qweight.shape[0]
+    lib = _native.lib()
+    most = (K // 64 + 1) // 2
+    splits = lib.wo_gemm_splits(M, N, K) if splits is None else max(1, min(int(splits), most))
+    y = torch.empty(M, N, dtype=x2.dtype, device=x2.device)
+    ws = torch.empty(splits * M * N, dtype=torch.float32, device=x2.device) if splits > 1 else None
+    lib.wo_gemm(_ptr(x2), _ptr(qweight), _ptr(scale), _ptr(bias), _ptr(y), _ptr(ws), M, N, K,
+                int(wdt == 'int4'), g, splits, act, _dt(x2), _stream())
+    return y
+
+
+def weight_only_linear(x, qweight, scale, bias=None, act=None, weight_dtype='int8', group_size=-1, splits=None):
+    """``act(x @ W + bias)`` for ``x`` [..., K] -> [..., N] in the dtype of ``x``, with
+    ``W = weight_dequantize(qweight, scale)`` never materialised on the ``'hip'`` path:
+    ``ops/csrc/wo_gemm.hip`` streams the integer levels once, multiplies them exactly (a level is
+    exact in bf16 / f16) and applies the fp32 scales to fp32 sums, per channel in the epilogue or
+    per group on the group's partial sum. ``act`` is None, ``'gelu'`` (erf) or ``'relu'``;
+    ``bias`` [N] is cast to the dtype of ``x``. ``splits`` overrides the kernel's split-K count
+    (``pra_wo_gemm_splits``); any count gives a bitwise reproducible result.
+
+    The kernel takes bf16 / f16 ``x`` with at most ``WO_MAX_ROWS`` rows, K % 64 == 0 and
+    N % 16 == 0. Anything else (and the CPU) runs the ``'ref'`` kernel, dequantise then the
+    library product in fp32, counted in ``registry.stats()`` as ``('weight_only_linear', 'ref')``."""
+    x, qweight, scale = getattr(x, '_t', x), getattr(qweight, '_t', qweight), getattr(scale, '_t', scale)
+    bias = getattr(bias, '_t', bias)
+    wdt, _ = _wo_algo(weight_dtype)
+    if act not in (None, 'none', 'gelu', 'relu'):
+        raise ValueError(f"weight_only_linear: act must be None, 'gelu' or 'relu', got {act!r}")
+    K, N, g = _wo_check(qweight, scale, wdt, group_size, K=x.shape[-1])
+    if bias is not None:
+        if bias.numel() != N:
+            raise ValueError(f"weight_only_linear: bias has {bias.numel()} values for N = {N}")
+        bias = bias.reshape(N).to(x.dtype).contiguous()
+    x2 = x.reshape(-1, K)
+    a = _ACT[act]
+    if x2.is_cuda and x2.dtype in _HALF and 1 <= x2.shape[0] <= WO_MAX_ROWS and _wo_tiled(K, N):
+        x2 = x2.contiguous()
+        if x2.data_ptr() % 16:
+            x2 = x2.clone()
+        y = R.dispatch('weight_only_linear', x2, x2, qweight.contiguous(), scale.contiguous(), bias, a, wdt, g,
+                       splits)
+    else:
+        R._STATS[('weight_only_linear', 'ref')] += 1
+        y = _wo_ref(x2, qweight, scale, bias, a, wdt, g)
+    return y.view(*x.shape[:-1], N)
