@@ -242,7 +242,7 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
                             quant_round_type=1, quant_max_bound=127.0, quant_min_bound=-127.0,
                             block_tables=None, qkv_weight_scales=None, linear_weight_scales=None,
                             ffn1_weight_scales=None, ffn2_weight_scales=None, weight_dtype=None,
-                            weight_group_size=-1):
+                            weight_group_size=-1, new_lens=None):
     """N transformer layers for inference / generation (parity: reference
     incubate/nn/functional/fused_transformer.py:872 and fused_multi_transformer_op.cu.h).
 
@@ -263,6 +263,13 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
       everything up to itself; ``rotary_embs`` is then [2, B, 1, S, D], row j for that position,
       and a mask row is shared by the S tokens. A sequence without room for all S tokens gets
       zero attention rows and no write.
+    * chunks of a prompt in the decode phase: with ``new_lens`` ([B] ints in [0, S]) sequence b
+      appends only its first ``new_lens[b]`` of the S rows (the rest is padding: zero attention
+      rows, nothing written; 0 is "no new tokens"), and the step runs ``ops.fused.mmha_prefill``:
+      the new K/V rows are appended, then attention runs over the cache on matrix instructions,
+      for any S. On the GPU a step without ``new_lens`` takes the same route once
+      (H / KVH) * S', S' = S rounded up to a power of two, exceeds ``ops.fused.MULTI_MAX_ROWS``;
+      steps within that limit keep ``mmha_decode_multi``.
     * grouped-query attention (``gqa_group_size`` = KVH > 0, the number of K/V heads): qkv
       weights are [H + 2*KVH, D, E] ([E, H + 2*KVH, D] with ``trans_qkvw=False``), biases
       [H + 2*KVH, D] — the query heads, then the k heads, then the v heads — and
@@ -407,11 +414,18 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
         if decode:
             if cache is None:
                 raise ValueError("fused_multi_transformer: time_step needs cache_kvs")
-            if S == 1:
+            if S == 1 and new_lens is None:
                 o = K.mmha_decode(qkv[:, 0].contiguous(), cache, t, mask, seq_lens=sl, rotary=krot,
                                   rotary_dims=rotary_emb_dims if krot is not None else 0,
                                   **({} if block_tables is None else {'block_tables': _t(block_tables)}),
                                   **qkw).reshape(B, 1, H * D)
+            elif new_lens is not None or (h.is_cuda and (H // (KVH or H)) * K._pow2_at_least(S) > K.MULTI_MAX_ROWS):
+                # a chunk of a prompt: append, then attend over the cache on matrix instructions
+                o = K.mmha_prefill(qkv.reshape(B, S, -1, D), cache, t, mask, seq_lens=sl, new_lens=_t(new_lens),
+                                   rotary=krot if S > 1 or krot is None else krot.reshape(2, B, 1, -1),
+                                   rotary_dims=rotary_emb_dims if krot is not None else 0,
+                                   **({} if block_tables is None else {'block_tables': _t(block_tables)}),
+                                   **qkw).reshape(B, S, H * D)
             else:                                    # S tokens per sequence in one pass over the cache
                 o = K.mmha_decode_multi(qkv.reshape(B, S, -1, D), cache, t, mask, seq_lens=sl, rotary=krot,
                                         rotary_dims=rotary_emb_dims if krot is not None else 0,

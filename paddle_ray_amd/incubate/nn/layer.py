@@ -208,7 +208,7 @@ class FusedMultiTransformer(Layer):
                 rotary_emb_dims=0, seq_lens=None, time_step=None, cache_k_quant_scales=None,
                 cache_v_quant_scales=None, cache_k_dequant_scales=None, cache_v_dequant_scales=None,
                 quant_round_type=1, quant_max_bound=127.0, quant_min_bound=-127.0,
-                block_tables=None):
+                block_tables=None, new_lens=None):
         return FF.fused_multi_transformer(
             src, self.ln_scales, self.ln_biases, self.qkv_weights, self.qkv_biases,
             self.linear_weights, self.linear_biases, self.ffn_ln_scales, self.ffn_ln_biases,
@@ -222,7 +222,7 @@ class FusedMultiTransformer(Layer):
             cache_k_dequant_scales=cache_k_dequant_scales,
             cache_v_dequant_scales=cache_v_dequant_scales, quant_round_type=quant_round_type,
             quant_max_bound=quant_max_bound, quant_min_bound=quant_min_bound,
-            block_tables=block_tables)
+            block_tables=block_tables, new_lens=new_lens)
 
 
 class FusedMultiTransformerDecoder:
@@ -295,8 +295,16 @@ class FusedMultiTransformerDecoder:
     place of ``argmax``, row j's token is drawn with slot b's temperature / top-k / top-p in one
     kernel and no host sync (``top_k=1`` is the ``argmax`` above); a draft is then accepted when it
     equals the token drawn for its row.
-    On the GPU T times the query heads per K/V head (T rounded up to a power of two) must not
-    exceed 8 (``ops.fused.MULTI_MAX_ROWS``).
+    On the GPU the multi-token decode kernel serves T times the query heads per K/V head (T
+    rounded up to a power of two) up to 8 (``ops.fused.MULTI_MAX_ROWS``); a taller step runs
+    ``ops.fused.mmha_prefill`` instead (append, then attention over the cache on matrix
+    instructions), inside the captured graph like the other, with that kernel's limits (f16 /
+    bf16, head dim 64 or 128, H / KVH in 1, 2, 4, 8; an fp32 model runs its torch definition).
+
+    Chunks of any length: ``extend(x, new_lens=None)`` (x [B, T, E]) appends up to T tokens per
+    slot at the slots' positions and advances them (``ops.fused.mmha_prefill``: append, then
+    attention over the cache on matrix instructions). It runs eagerly beside the captured graphs:
+    a chunked prefill from an empty decoder, a follow-up turn, a long prompt admitted in pieces.
 
     Weight-only int8 / int4: ``weight_only='int8'`` or ``'int4'`` (``weight_group_size`` -1 for one
     scale per output channel, or 64 / 128) quantises the model's qkv, out-projection, FFN1 and FFN2
@@ -400,6 +408,7 @@ class FusedMultiTransformerDecoder:
         self._out = None
         self._multi = {}              # T -> [x buffer [B, T, E], captured graph, its output]
         self._last_T = None           # T of the step_multi that commit() may follow
+        self._scaled = [not self.dynamic_scales] * self.B    # slots whose cache scales are set
 
     def _caches(self):
         from ...framework.core import Tensor
@@ -439,7 +448,8 @@ class FusedMultiTransformerDecoder:
 
     def prefill(self, x, attn_mask=None, seq_lens=None):
         """Context phase over the prompt (caches filled in place); decode continues at S0, or
-        with ``seq_lens`` ([B], right-padded prompts) at every sequence's own length."""
+        with ``seq_lens`` ([B], right-padded prompts) at every sequence's own length. ``extend``
+        appends further chunks to what is cached, or the whole prompt in pieces."""
         from ...framework.core import Tensor
         import torch
         xt = x._t if hasattr(x, '_t') else x
@@ -554,12 +564,14 @@ class FusedMultiTransformerDecoder:
         self._set_row(b, [])
         self.lens[b].fill_(self.MB * self.BS)
         self._pos[b] = None
+        self._scaled[b] = not self.dynamic_scales
 
     def admit(self, b, x, attn_mask=None):
         """A new prompt ``x`` [1, S, E] joins the running batch in the released (or unused) slot
         ``b``: blocks are allocated, the context phase runs for this one sequence through table
         row ``b`` and the slot continues at position ``S``. Returns the prompt's output
-        [1, S, E]; the other slots and the captured step graph are untouched."""
+        [1, S, E]; the other slots and the captured step graph are untouched. ``extend`` with
+        ``new_lens`` zero elsewhere appends a long prompt's later pieces between decode steps."""
         from ...framework.core import Tensor
         import torch
         self._need_paged('admit')
@@ -607,6 +619,7 @@ class FusedMultiTransformerDecoder:
         import torch
         from ...ops import fused as K
         rows = slice(None) if slot is None else slice(slot, slot + 1)
+        self._scaled[rows] = [True] * len(self._scaled[rows])
         S0 = kv[0].shape[3]
         pad = None
         if seq_lens is not None:
@@ -701,6 +714,88 @@ class FusedMultiTransformerDecoder:
                 ent[1] = g
             ent[1].replay()
         return Tensor(ent[2].clone())
+
+    def extend(self, x, new_lens=None):
+        """Append a chunk of tokens to every live slot at its current position and advance:
+        ``x`` is [B, T, E] for any T, slot ``b`` takes its first ``new_lens[b]`` rows (a list, array
+        or tensor of B counts in [0, T]; default T; a released slot takes 0). Returns [B, T, E], row
+        j what the j-th of that many ``step`` calls would return; padded rows are unspecified but
+        finite. Attention runs ``ops.fused.mmha_prefill``: the chunk's K/V are appended, then the
+        chunk attends over the cache on matrix instructions, so the cost does not depend on how the
+        prompt was cut. It works right after construction too: ``extend`` in chunks is a chunked
+        prefill, ``extend`` on a prefilled decoder a follow-up turn.
+
+        It runs eagerly (chunk lengths vary) and leaves the captured ``step`` / ``step_multi``
+        graphs alone. Paged mode first allocates the blocks covering [p, p + n_b) of every slot and
+        raises ``RuntimeError`` before it changes anything when the free list is short; without
+        paging one sync reads the positions to check the room. With ``weight_only`` a chunk of more
+        than ``ops.fused.WO_MAX_ROWS`` rows takes the dequantise-then-float products. Dynamic int8
+        scales are the slot's existing ones (later tokens saturate, as in ``step``); a slot whose
+        scales were never set by ``prefill`` / ``admit`` raises."""
+        import torch
+        from ...framework.core import Tensor
+        xt = x._t if hasattr(x, '_t') else x
+        if xt.dim() != 3 or xt.shape[0] != self.B or xt.shape[1] < 1:
+            raise ValueError(f"FusedMultiTransformerDecoder.extend: x must be [{self.B}, T, E] with T >= 1, "
+                             f"got {tuple(xt.shape)}")
+        T = int(xt.shape[1])
+        if new_lens is None:
+            counts = [T] * self.B
+        else:
+            a = new_lens._t if hasattr(new_lens, '_t') else new_lens
+            counts = [int(n) for n in torch.as_tensor(a).reshape(-1).tolist()]
+            if len(counts) != self.B or not all(0 <= n <= T for n in counts):
+                raise ValueError(f"FusedMultiTransformerDecoder.extend: need {self.B} counts in [0, {T}], "
+                                 f"got {counts}")
+        if self.paged:
+            counts = [0 if p is None else n for n, p in zip(counts, self._pos)]
+            pos = [0 if p is None else p for p in self._pos]
+        else:
+            pos = self.lens.tolist() if self.ragged else [int(self.t)] * self.B
+        if any(p + n > self.L for p, n in zip(pos, counts)):
+            raise ValueError(f"FusedMultiTransformerDecoder.extend: positions {pos} plus {counts} new tokens "
+                             f"exceed max_seq_len {self.L}")
+        if self.dynamic_scales and any(n and not s for n, s in zip(counts, self._scaled)):
+            raise RuntimeError("FusedMultiTransformerDecoder.extend: dynamic int8 cache scales come from a "
+                               "prompt; prefill or admit the slot first")
+        if self.paged:                # blocks first: an exhausted pool raises with nothing changed
+            want = [(b, (p + n - 1) // self.BS + 1 - len(self._blocks[b]))
+                    for b, (p, n) in enumerate(zip(pos, counts)) if n]
+            want = [(b, k) for b, k in want if k > 0]
+            if sum(k for _, k in want) > len(self._free):
+                raise RuntimeError(f"FusedMultiTransformerDecoder.extend: the chunk needs "
+                                   f"{sum(k for _, k in want)} new blocks and {len(self._free)} are free; "
+                                   "release a slot or use a larger pool")
+            for b, k in want:
+                for _ in range(k):
+                    e = self._free.pop()
+                    self.tables[b, len(self._blocks[b])].fill_(e)
+                    self._blocks[b].append(e)
+        if not self.ragged:           # every slot continues from the common position, on its own
+            self.lens.copy_(self.t.expand(self.B))
+            self.ragged, self._graph = True, None
+        nl = torch.tensor(counts, dtype=torch.int32).to(self.dev)
+        kw = dict(self._qkw)
+        kw.update(seq_lens=Tensor(self.lens), new_lens=Tensor(nl))
+        if self.paged:
+            kw['block_tables'] = Tensor(self.tables)
+        if self.rot is not None:      # token j of a slot: the row of its position + j
+            at = (self.lens[:, None] + torch.arange(T, device=self.dev, dtype=torch.int32)[None, :]
+                  ).clamp(max=self.L - 1)
+            r = self.rot.index_select(1, at.reshape(-1)).view(2, self.B, 1, T, -1)
+            kw.update(rotary_embs=Tensor(r), rotary_emb_dims=self.rot_dims)
+        with torch.no_grad():
+            out, _ = self._model(Tensor(xt.to(self.dtype)), self._caches(), attn_mask=Tensor(self.mask),
+                                 time_step=Tensor(self.t), **kw)
+        self.lens.add_(nl)
+        if self.paged:
+            self._pos = [p if p is None else p + n for n, p in zip(counts, self._pos)]
+            live = [p for p in self._pos if p is not None]
+            self.t.fill_(max(live) if live else 0)
+        else:
+            self.t.fill_(max(p + n for p, n in zip(pos, counts)))
+        self._last_T = None           # rows of an uncommitted step_multi are overwritten
+        return out
 
     def commit(self, accepted):
         """After ``step_multi``: slot ``b`` keeps the first ``accepted[b]`` (in [0, T]) of its T

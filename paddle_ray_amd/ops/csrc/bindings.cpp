@@ -114,6 +114,12 @@ PYBIND11_MODULE(_pra_hip, m) {
   Launch<&pra_mmha_decode_multi>::def(m, "mmha_decode_multi",
                                       "n_tok < 1, more than 8 query rows per K/V row, or anything mmha_decode / "
                                       "mmha_decode_paged refuses");
+  // T new tokens per sequence appended to the cache and attended over it with matrix instructions, any
+  // T (contract above the definition in prefill_attn.hip); a null block table means the contiguous cache
+  Launch<&pra_mmha_prefill>::def(m, "mmha_prefill",
+                                 "dtype not f16 / bf16, head_dim not 64 / 128, group ratio not 1 / 2 / 4 / 8, block "
+                                 "size not a power of two >= 16, misaligned buffers, or unsupported rotary_dims / "
+                                 "quantisation arguments; or the runtime refused the attend kernel's LDS size");
   // temperature / top-k / top-p sampling, one id per row (contract above the definition in sample.hip)
   Launch<&pra_sample_top_p>::def(m, "sample_top_p", "unsupported dtype, R < 0, V < 1 or V > 2^22");
   // weight-only int8 / int4 linear for at most 64 rows (contract above the definition in wo_gemm.hip)

@@ -84,6 +84,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "kv_rows.h"
 #include "pra_api.h"
 
 namespace pra {
@@ -126,17 +127,6 @@ __device__ __forceinline__ void merge(float& m, float& l, float* a, float m2, fl
   m = M;
 }
 
-// x[8] (dims d0.. of one head row) rotated against its partner half a chunk away; c / s are
-// the lane's 8 cos / sin values, shared by every row the lane rotates
-template <typename T>
-__device__ __forceinline__ void rotate8(const T* row, int d0, int half, bool left, const float* c, const float* s,
-                                        float* x) {
-  float p[8];
-  load8<T>(row + (left ? d0 + half : d0 - half), p);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) x[i] = left ? x[i] * c[i] - p[i] * s[i] : x[i] * c[i] + p[i] * s[i];
-}
-
 // what only a Q8 instantiation is given (an empty parameter otherwise)
 template <bool Q8> struct QParams {};
 template <> struct QParams<true> {
@@ -146,27 +136,7 @@ template <> struct QParams<true> {
   float qmax, qmin;     // level bounds, -128 <= qmin < qmax <= 127
 };
 
-// 8 values -> 8 stored bytes: level = clamp(round(x * qs)), byte = level + 128. One fp32
-// multiply, then the rounding; contraction is off so that the product is rounded before it
-// is used, exactly as x * qs is in torch
-__device__ __forceinline__ uint2 quant8(const float* x, float qs, int round_type, float qmax, float qmin) {
-#pragma clang fp contract(off)
-  uint32_t w[2] = {0u, 0u};
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const float y = x[i] * qs;
-    float r;
-    if (round_type == 0) {
-      r = rintf(y);
-    } else {  // y - trunc(y) is exact
-      const float tr = truncf(y);
-      r = tr + (fabsf(y - tr) >= 0.5f ? copysignf(1.f, y) : 0.f);
-    }
-    r = fminf(fmaxf(r, qmin), qmax);
-    w[i >> 2] |= (uint32_t)((int)r + 128) << (8 * (i & 3));
-  }
-  return make_uint2(w[0], w[1]);
-}
+// rotate8 (the rotary rule) and quant8 (8 values -> 8 stored bytes) are kv_rows.h's
 
 // 8 stored bytes -> 8 floats in [0, 255] (v_cvt_f32_ubyte0..3); the offset is applied elsewhere
 __device__ __forceinline__ void unpack8(uint2 w, float* o) {

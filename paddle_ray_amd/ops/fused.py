@@ -1515,6 +1515,252 @@ def mmha_decode_multi(qkv, cache, time_step, mask=None, seq_lens=None, rotary=No
                       tables=tables)
 
 
+# --- prefill over the cache: any number of new tokens per sequence, on matrix instructions ------
+PREFILL_RATIOS = (1, 2, 4, 8)   # query heads per K/V head the HIP prefill kernel is built for
+
+
+@R.register_kernel('mmha_prefill', 'ref')
+def _mmha_prefill_ref(qkv, cache, t, mask, seq_lens=None, new_lens=None, rotary=None, rotary_dims=0, quant=None,
+                      tables=None):
+    """The definition of the prefill step, per sequence: the all-or-nothing guard, the n_b new
+    rows rounded or quantised under ``mmha_decode``'s rule and written at [t_b, t_b + n_b) in one
+    assignment, then the causal softmax over the cached [0, t_b + n_b) in fp32, row by row.
+    ``tables`` (int [B, MB]) makes ``cache`` the block pool; a block whose entry is outside the
+    pool is read as masked keys.
+
+    It is a definition, not a fast path: host lists of the positions (a sync for device tensors)
+    and two small einsums per query row, B * T rows in all. The HIP kernel is registered for f16
+    and bf16 only, so an fp32 call on the GPU runs this; ``fused_multi_transformer`` sends fp32
+    decode-phase steps beyond ``MULTI_MAX_ROWS`` here, where they used to raise."""
+    B, T, N, D = qkv.shape
+    KVH = cache.shape[2]
+    H = N - 2 * KVH
+    rep = H // KVH
+    paged = tables is not None
+    NB, BS = cache.shape[1], cache.shape[3]
+    L = tables.shape[1] * BS if paged else BS
+    tt = int(t.reshape(-1)[0]) if isinstance(t, torch.Tensor) else int(t)
+    lens = [tt] * B if seq_lens is None else [int(n) for n in seq_lens.reshape(-1).tolist()]
+    news = [T] * B if new_lens is None else [int(n) for n in new_lens.reshape(-1).tolist()]
+    mrows = None if mask is None else mask.reshape(B, -1).float()
+    row = qkv.float()
+    q, k, v = row[:, :, :H], row[:, :, H:H + KVH], qkv[:, :, H + KVH:]
+    if rotary is not None:
+        cos, sin = rotary.reshape(2, B * T, D).float().to(qkv.device)
+        q = _rotate_rows(q.reshape(B * T, H, D), cos, sin, rotary_dims).reshape(B, T, H, D)
+        k = _rotate_rows(k.reshape(B * T, KVH, D), cos, sin, rotary_dims).reshape(B, T, KVH, D)
+    if quant is not None:
+        scales, _, round_type, qmax, qmin = quant
+        kq, vq, kdq, vdq = scales.to(qkv.device).expand(4, B, KVH)
+        k = kv_quantize(k.transpose(1, 2), kq, round_type, qmax, qmin).transpose(1, 2)   # [B, T, KVH, D] bytes
+        v = kv_quantize(v.float().transpose(1, 2), vq, round_type, qmax, qmin).transpose(1, 2)
+    else:
+        k = k.to(qkv.dtype)                                       # rounded once, as cached
+    tab = tables.to(device=cache.device, dtype=torch.long) if paged else None
+    out = torch.zeros(B, T, H, D, device=qkv.device, dtype=torch.float32)
+    for b, (tb, n) in enumerate(zip(lens, news)):
+        if not (tb >= 0 and 0 < n <= T and tb + n <= L and (mrows is None or mrows.shape[1] >= tb + n)):
+            continue                                              # guarded, or no new tokens: zeros, no write
+        end = tb + n
+        pos = torch.arange(tb, end, device=cache.device)
+        if paged:
+            ent = tab[b, :(end - 1) // BS + 1]
+            ok = (ent >= 0) & (ent < NB)
+            if not bool(ok[tb // BS:].all()):
+                continue                                          # a new position without a block
+            cache[0, tab[b, pos // BS], :, pos % BS] = k[b, :n]
+            cache[1, tab[b, pos // BS], :, pos % BS] = v[b, :n]
+            g = cache[:, ent.clamp(0, NB - 1)].permute(0, 2, 1, 3, 4).reshape(2, KVH, -1, D)[:, :, :end]
+            hidden = (~ok).repeat_interleave(BS)[:end]            # keys of a block that is not there
+            g = torch.where(hidden[None, None, :, None], torch.full_like(g[:1, :1, :1, :1], 128 if quant else 0), g)
+        else:
+            cache[0, b, :, tb:end] = k[b, :n].transpose(0, 1)
+            cache[1, b, :, tb:end] = v[b, :n].transpose(0, 1)
+            g, hidden = cache[:, b, :, :end], None
+        if quant is not None:
+            K_ = kv_dequantize(g[0][None], kdq[b:b + 1])[0]
+            V_ = kv_dequantize(g[1][None], vdq[b:b + 1])[0]
+        else:
+            K_, V_ = g[0].float(), g[1].float()
+        if rep > 1:                                               # query head h reads K/V head h // rep
+            K_, V_ = K_.repeat_interleave(rep, 0), V_.repeat_interleave(rep, 0)
+        bias = None if mrows is None else mrows[b, None, :end]
+        if hidden is not None:
+            bias = torch.zeros(1, end, device=qkv.device) if bias is None else bias
+            bias = bias.masked_fill(hidden.to(bias.device)[None, :], float('-inf'))
+        # the causal softmax, one query row at a time over the keys it sees: reductions of the
+        # single-token step's own shapes, so the result equals that step bit for bit (one padded
+        # [n, end] softmax sums in another order and differs in the last place)
+        for j in range(n):
+            s = torch.einsum('hd,hld->hl', q[b, j], K_[:, :tb + j + 1]) / math.sqrt(D)
+            if bias is not None:
+                s = s + bias[:, :tb + j + 1]
+            out[b, j] = torch.einsum('hl,hld->hd', torch.softmax(s, -1), V_[:, :tb + j + 1])
+    return out.to(qkv.dtype)
+
+
+@R.register_kernel('mmha_prefill', 'hip', dtypes=_HALF)
+def _mmha_prefill_hip(qkv, cache, t, mask, seq_lens=None, new_lens=None, rotary=None, rotary_dims=0, quant=None,
+                      tables=None):
+    B, T, N, D = qkv.shape
+    KVH = cache.shape[2]
+    H = N - 2 * KVH
+    if H // KVH not in PREFILL_RATIOS:
+        raise ValueError(f"mmha_prefill: {H} query heads over {KVH} K/V heads is a ratio of {H // KVH}; the HIP "
+                         f"kernel supports {PREFILL_RATIOS}")
+    if D not in (64, 128):
+        raise ValueError(f"mmha_prefill: head_dim {D} is not supported by the HIP kernel (64 or 128)")
+    if tables is None:
+        L, NB, BS, MB = cache.shape[3], 0, cache.shape[3], 1
+    else:
+        NB, BS, MB = cache.shape[1], cache.shape[3], tables.shape[1]
+        L = MB * BS
+        if BS < 16 or BS & (BS - 1):
+            raise ValueError(f"mmha_prefill: block size {BS} is not supported by the HIP kernel (a power of "
+                             "two >= 16)")
+        if not (tables.is_cuda and tables.dtype == torch.int32 and tables.is_contiguous() and
+                tables.dim() == 2 and tables.shape[0] == B):
+            raise ValueError(f"mmha_prefill: block_tables must be a contiguous CUDA int32 [{B}, MB] tensor")
+    cache_ok = cache.dtype == qkv.dtype if quant is None else (cache.dtype == torch.uint8 and cache.is_cuda)
+    if not (qkv.is_contiguous() and cache.is_contiguous() and cache_ok and cache.data_ptr() % 16 == 0 and
+            (tuple(cache.shape) == (2, B, KVH, L, D) if tables is None else tuple(cache.shape[2:]) == (KVH, BS, D))):
+        raise ValueError(f"mmha_prefill: qkv {tuple(qkv.shape)} {qkv.dtype} / cache {tuple(cache.shape)} "
+                         f"{cache.dtype} not supported by the HIP kernel")
+    for name, x in (('seq_lens', seq_lens), ('new_lens', new_lens)):
+        if x is not None and not (x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() and x.numel() == B):
+            raise ValueError(f"mmha_prefill: {name} must be a contiguous CUDA int32 [{B}] tensor")
+    # the position of every sequence when there is no seq_lens: a host value for the launch
+    t = 0 if seq_lens is not None else int(t.reshape(-1)[0]) if isinstance(t, torch.Tensor) else int(t)
+    if rotary is not None:
+        if not rotary_in_kernel(D, rotary_dims):
+            raise ValueError(f"mmha_prefill: head_dim {D} with rotary_dims={rotary_dims} is not supported by the "
+                             "HIP kernel (half a chunk must be a multiple of 8)")
+        if not (rotary.is_cuda and rotary.dtype == torch.float32 and rotary.is_contiguous() and
+                tuple(rotary.shape) == (2, B, T, D)):
+            raise ValueError(f"mmha_prefill: rotary must be a contiguous CUDA fp32 [2, {B}, {T}, {D}] tensor")
+    mlen = 0
+    if mask is not None:
+        mask = mask.reshape(B, -1).float().contiguous()
+        mlen = mask.shape[1]
+    if quant is not None:
+        scales, bstride, round_type, qmax, qmin = quant
+        if not (scales.is_cuda and scales.dtype == torch.float32 and scales.is_contiguous() and
+                tuple(scales.shape) == (4, B if bstride else 1, KVH) and bstride in (0, KVH)):
+            raise ValueError(f"mmha_prefill: the packed cache scales must be a contiguous CUDA fp32 "
+                             f"[4, 1 or {B}, {KVH}] tensor")
+        cache_dt, scales_ptr = _CACHE_U8, _ptr(scales)
+    else:
+        cache_dt, scales_ptr, bstride, round_type, qmax, qmin = _dt(qkv), 0, 0, 1, 127.0, -127.0
+    out = torch.empty(B, T, H, D, device=qkv.device, dtype=qkv.dtype)   # every row is written
+    _native.lib().mmha_prefill(_ptr(qkv), _ptr(cache), _ptr(mask) if mask is not None else 0, _ptr(out),
+                               B, T, H, KVH, NB, BS, MB, D, t, mlen, 1.0 / math.sqrt(D), _dt(qkv),
+                               _ptr(seq_lens) if seq_lens is not None else 0,
+                               _ptr(new_lens) if new_lens is not None else 0,
+                               _ptr(rotary) if rotary is not None else 0, int(rotary_dims), _stream(),
+                               cache_dt, scales_ptr, bstride, round_type, qmax, qmin,
+                               _ptr(tables) if tables is not None else 0)
+    return out
+
+
+def mmha_prefill(qkv, cache, time_step, mask=None, seq_lens=None, new_lens=None, rotary=None, rotary_dims=0,
+                 cache_k_quant_scales=None, cache_v_quant_scales=None, cache_k_dequant_scales=None,
+                 cache_v_dequant_scales=None, quant_round_type=1, quant_max_bound=127.0,
+                 quant_min_bound=-127.0, block_tables=None):
+    """Append up to T new tokens per sequence to a cache that may already hold positions, and
+    attend: equal to that many consecutive ``mmha_decode`` steps, for any T (a chunk of a prompt,
+    a follow-up turn, a whole prompt from an empty cache). ``qkv`` is [B, T, H + 2*KVH, D] and the
+    result [B, T, H, D]. Sequence b has ``t_b`` cached positions (``seq_lens[b]``, or
+    ``time_step`` without ``seq_lens``) and ``n_b`` new tokens (``new_lens[b]`` in [0, T], its rows
+    right-padded; T without ``new_lens``). Token j < n_b is cached at ``t_b + j`` under
+    ``mmha_decode``'s rule for a float or a ``uint8`` cache and attends to [0, t_b + j]; rows
+    j >= n_b come back zero and write nothing, and ``n_b = 0`` is "no new tokens". The additive
+    ``mask`` [B, mask_len] is per key position and shared by the T tokens; ``rotary`` is
+    [2, B, T, D], row j the cos / sin of position ``t_b + j``. ``cache``, the quantisation
+    arguments and ``block_tables`` are ``mmha_decode``'s.
+
+    Host values are validated (``new_lens`` in [0, T]; 0 <= t_b <= time_step and t_b + n_b <= L;
+    with a host table every block covering [0, t_b + n_b) in [0, NB) and no two sequences
+    appending to the same block). Device values are not synced; a sequence is then guarded as a
+    whole, zeros and no write at all, when t_b < 0, t_b + n_b > L, the mask is shorter than
+    t_b + n_b, or a block holding one of its new positions has a table entry outside [0, NB). On
+    the GPU: f16 or bf16, head dim 64 or 128, H / KVH in ``PREFILL_RATIOS``, block size a power of
+    two >= 16."""
+    if qkv.dim() != 4 or qkv.shape[1] < 1:
+        raise ValueError(f"mmha_prefill: qkv must be [B, T, H + 2*KVH, D] with T >= 1, got {tuple(qkv.shape)}")
+    B, T, N, D = qkv.shape
+    if not isinstance(time_step, torch.Tensor):
+        time_step = int(time_step)
+    paged = block_tables is not None
+    if cache.dim() != 5 or cache.shape[0] != 2 or cache.shape[4] != D or (not paged and cache.shape[1] != B):
+        raise ValueError(f"mmha_prefill: cache {tuple(cache.shape)} does not fit qkv {tuple(qkv.shape)}; "
+                         f"need {'the block pool [2, NB, KVH, BS, D]' if paged else '[2, B, KVH, L, D]'}")
+    KVH = cache.shape[2]
+    H = N - 2 * KVH
+    if H <= 0 or H % KVH != 0:
+        raise ValueError(f"mmha_prefill: qkv has {N} head rows and the cache {KVH} K/V heads; "
+                         f"{N} - 2*{KVH} query heads must be a positive multiple of {KVH}")
+    tables = None
+    if paged:
+        tables = torch.as_tensor(block_tables)
+        if tables.dim() != 2 or tables.shape[0] != B or tables.shape[1] < 1 or tables.dtype.is_floating_point:
+            raise ValueError(f"mmha_prefill: block_tables must be an integer [{B}, MB] table, got "
+                             f"{tuple(tables.shape)} {tables.dtype}")
+    L = tables.shape[1] * cache.shape[3] if paged else cache.shape[3]
+    quant = _kv_quant_args(B, cache, cache_k_quant_scales, cache_v_quant_scales, cache_k_dequant_scales,
+                           cache_v_dequant_scales, quant_round_type, quant_max_bound, quant_min_bound,
+                           qkv.device)
+    host = not isinstance(time_step, torch.Tensor) or (not paged and not time_step.is_cuda)
+    news = None
+    for name, x in (('seq_lens', seq_lens), ('new_lens', new_lens)):
+        if x is not None:
+            host = host and not (isinstance(x, torch.Tensor) and x.is_cuda)
+            if torch.as_tensor(x).numel() != B:
+                raise ValueError(f"mmha_prefill: {name} has {torch.as_tensor(x).numel()} entries for batch {B}")
+    if seq_lens is not None:
+        seq_lens = torch.as_tensor(seq_lens).reshape(-1)
+    if new_lens is not None:
+        new_lens = torch.as_tensor(new_lens).reshape(-1)
+        if not new_lens.is_cuda:
+            news = [int(n) for n in new_lens.tolist()]
+            if not all(0 <= n <= T for n in news):
+                raise ValueError(f"mmha_prefill: new_lens must lie in [0, {T}], got {news}")
+    if host:
+        ts = int(time_step)
+        lens = [ts] * B if seq_lens is None else [int(n) for n in seq_lens.tolist()]
+        news = [T] * B if news is None else news
+        if not all(0 <= n <= ts and n + m <= L for n, m in zip(lens, news)):
+            raise ValueError(f"mmha_prefill: need 0 <= seq_lens <= time_step and seq_lens + new_lens <= {L}, "
+                             f"got seq_lens={lens} new_lens={news} time_step={ts}")
+        if paged and not tables.is_cuda:
+            NB, BS, rows, owner = cache.shape[1], cache.shape[3], tables.tolist(), {}
+            for b, (n, m) in enumerate(zip(lens, news)):
+                if m == 0:
+                    continue
+                bad = [e for e in rows[b][:(n + m - 1) // BS + 1] if not 0 <= e < NB]
+                if bad:
+                    raise ValueError(f"mmha_prefill: block_tables[{b}] covers positions [0, {n + m}) with "
+                                     f"entry {bad[0]}, outside the pool's [0, {NB})")
+                for e in set(rows[b][n // BS:(n + m - 1) // BS + 1]):
+                    if owner.setdefault(e, b) != b:
+                        raise ValueError(f"mmha_prefill: two sequences append to the same block ({e}, "
+                                         f"sequences {owner[e]} and {b}); only blocks that are read may be "
+                                         "shared")
+    if paged:
+        tables = tables.to(device=qkv.device, dtype=torch.int32).contiguous()
+    if seq_lens is not None:
+        seq_lens = seq_lens.to(device=qkv.device, dtype=torch.int32).contiguous()
+    if new_lens is not None:
+        new_lens = new_lens.to(device=qkv.device, dtype=torch.int32).contiguous()
+    if rotary is not None:
+        if isinstance(rotary, (tuple, list)):
+            rotary = torch.stack([torch.as_tensor(r).reshape(B, T, D) for r in rotary])
+        if int(rotary_dims) < 1:
+            raise ValueError("mmha_prefill: rotary needs rotary_dims >= 1")
+        rotary = rotary.reshape(2, B, T, D).to(device=qkv.device, dtype=torch.float32).contiguous()
+    return R.dispatch('mmha_prefill', qkv, qkv.contiguous(), cache, time_step, mask, seq_lens=seq_lens,
+                      new_lens=new_lens, rotary=rotary, rotary_dims=int(rotary_dims), quant=quant, tables=tables)
+
+
 # =============================================================================
 # bias + GELU
 # =============================================================================
