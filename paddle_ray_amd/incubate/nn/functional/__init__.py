@@ -541,3 +541,25 @@ def fused_ec_moe(x, gate, bmm0_weight, bmm0_bias, bmm1_weight, bmm1_bias, act_ty
     h = torch.nn.functional.gelu(h) if act_type == 'gelu' else torch.relu(h)
     o = torch.einsum('bsef,efd->bsed', h, _u(bmm1_weight)) + _u(bmm1_bias).squeeze(1)
     return Tensor((o * g.unsqueeze(-1)).sum(2))
+
+
+def fused_moe(x, gate_weight, ffn1_weight, ffn2_weight, ffn1_bias=None, ffn1_scale=None, ffn2_bias=None,
+              ffn2_scale=None, quant_method='None', moe_topk=2, norm_topk_prob=True):
+    """Top-k routed mixture-of-experts FFN (parity: python/paddle/incubate/nn/functional/fused_moe.py).
+    ``x`` [B, S, D]; ``gate_weight`` fp32 [D, E]; ``ffn1_weight`` [E, D, N1]; ``ffn2_weight``
+    [E, F, D]; biases [E, 1, N1] / [E, 1, D]. The activation follows the weights: N1 == 2F is
+    SwiGLU, N1 == F is GELU. Each token goes through its ``moe_topk`` best experts only
+    (``ops.fused.moe_route`` / ``moe_ffn``; at decode sizes on the GPU the kernels of
+    ``ops/csrc/moe_ffn.hip``). Quantised expert weights are not implemented."""
+    if quant_method != 'None' or ffn1_scale is not None or ffn2_scale is not None:
+        raise NotImplementedError(f"fused_moe: quantised expert weights (quant_method = {quant_method!r}, "
+                                  "ffn1_scale / ffn2_scale) are not implemented")
+    t, w1, w2 = _u(x), _u(ffn1_weight), _u(ffn2_weight)
+    if w1.dim() != 3 or w2.dim() != 3 or w1.shape[-1] not in (w2.shape[1], 2 * w2.shape[1]):
+        raise ValueError(f"fused_moe: ffn1_weight [E, D, F or 2F] / ffn2_weight [E, F, D] expected, got "
+                         f"{tuple(w1.shape)} / {tuple(w2.shape)}")
+    act = 'swiglu' if w1.shape[-1] == 2 * w2.shape[1] else 'gelu'
+    ids, w = K.moe_route(t, _u(gate_weight), moe_topk, norm_topk_prob)
+    b1 = None if ffn1_bias is None else _u(ffn1_bias)
+    b2 = None if ffn2_bias is None else _u(ffn2_bias)
+    return Tensor(K.moe_ffn(t, ids, w, w1, w2, b1, b2, act))

@@ -4643,3 +4643,163 @@ def weight_only_linear(x, qweight, scale, bias=None, act=None, weight_dtype='int
         R._STATS[('weight_only_linear', 'ref')] += 1
         y = _wo_ref(x2, qweight, scale, bias, a, wdt, g)
     return y.view(*x.shape[:-1], N)
+
+
+# =============================================================================
+# Top-k routed mixture-of-experts FFN for decode steps (moe_ffn.hip). Parity: the reference's
+# python/paddle/incubate/nn/functional/fused_moe.py.
+# =============================================================================
+MOE_MAX_ROWS = 64        # tokens the HIP kernels take; taller inputs (prefill) run the ref kernels
+MOE_MAX_EXPERTS = 256
+MOE_MAX_TOPK = 8
+_MOE_ACT = {'gelu': 1, 'relu': 3, 'swiglu': 4}
+
+
+def _moe_route_check(x, gate_weight, top_k):
+    if gate_weight.dim() != 2 or gate_weight.shape[0] != x.shape[-1] or gate_weight.dtype != torch.float32:
+        raise ValueError(f"moe_route: gate_weight must be fp32 [D, E] for x {tuple(x.shape)}, got "
+                         f"{gate_weight.dtype} {tuple(gate_weight.shape)}")
+    E, k = gate_weight.shape[1], int(top_k)
+    if not 1 <= k <= E:
+        raise ValueError(f"moe_route: top_k = {top_k} outside [1, E = {E}] for gate_weight "
+                         f"{tuple(gate_weight.shape)}")
+    return E, k
+
+
+def _moe_in_limits(x2, E, k, *dims):
+    return (x2.is_cuda and x2.dtype in _HALF and 1 <= x2.shape[0] <= MOE_MAX_ROWS and E <= MOE_MAX_EXPERTS
+            and k <= MOE_MAX_TOPK and all(d % 64 == 0 for d in dims))
+
+
+@R.register_kernel('moe_route', 'ref')
+def _moe_route_ref(x2, gate_weight, k, norm):
+    """Stable descending sort of the fp32 logits; softmax over all experts at the k first."""
+    logits = x2.float() @ gate_weight
+    ids = torch.sort(logits, dim=-1, descending=True, stable=True).indices[:, :k]
+    w = torch.softmax(logits, -1).gather(1, ids)
+    if norm:
+        s = w[:, 0]
+        for j in range(1, k):
+            s = s + w[:, j]
+        w = w / s[:, None]
+    return ids.to(torch.int32), w
+
+
+@R.register_kernel('moe_route', 'hip', dtypes=_HALF)
+def _moe_route_hip(x2, gate_weight, k, norm):
+    M, D = x2.shape
+    E = gate_weight.shape[1]
+    ids = torch.empty(M, k, dtype=torch.int32, device=x2.device)
+    w = torch.empty(M, k, dtype=torch.float32, device=x2.device)
+    _native.lib().moe_route(_ptr(x2), _ptr(gate_weight), _ptr(ids), _ptr(w), M, D, E, k, int(bool(norm)),
+                            _dt(x2), _stream())
+    return ids, w
+
+
+def _aligned(t):
+    t = t.contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def moe_route(x, gate_weight, top_k, norm_topk_prob=True):
+    """Top-k routing of the tokens ``x`` [..., D] under ``gate_weight`` (fp32 [D, E]): returns
+    ``(ids, weights)``, int32 and fp32 ``[M, top_k]`` over the M flattened tokens. The logits
+    ``x @ gate_weight`` are fp32; the ``top_k`` largest win in the order of a stable descending
+    sort (ties to the lower expert); the weights are ``softmax(logits)`` over all E experts at
+    the winners, divided by their own sum (added in slot order) with ``norm_topk_prob``.
+
+    ``ops/csrc/moe_ffn.hip`` takes bf16 / f16 tokens on the GPU with at most ``MOE_MAX_ROWS`` rows,
+    E <= 256, top_k <= 8 and D % 64 == 0; anything else runs the ``'ref'`` kernel, counted in
+    ``registry.stats()`` as ``('moe_route', 'ref')``."""
+    x, gate_weight = getattr(x, '_t', x), getattr(gate_weight, '_t', gate_weight)
+    E, k = _moe_route_check(x, gate_weight, top_k)
+    x2 = x.reshape(-1, x.shape[-1])
+    if _moe_in_limits(x2, E, k, x2.shape[1]):
+        return R.dispatch('moe_route', x2, _aligned(x2), gate_weight.contiguous(), k, norm_topk_prob)
+    R._STATS[('moe_route', 'ref')] += 1
+    return _moe_route_ref(x2, gate_weight, k, norm_topk_prob)
+
+
+@R.register_kernel('moe_ffn', 'ref')
+def _moe_ffn_ref(x2, ids, tw, w1, w2, b1, b2, act):
+    """Experts looped over their index-selected rows, products in fp32, h rounded to the dtype of
+    x, the slots of a token combined in slot order."""
+    M, D = x2.shape
+    k, flat = ids.shape[1], ids.reshape(-1).long()
+    slots = torch.zeros(M * k, D, dtype=torch.float32, device=x2.device)
+    for e in flat.unique().tolist():
+        sel = (flat == e).nonzero().squeeze(1)
+        z = x2[sel // k].float() @ w1[e].float()
+        if b1 is not None:
+            z = z + b1[e].float()
+        if act == 4:
+            F = z.shape[1] // 2
+            h = torch.nn.functional.silu(z[:, :F]) * z[:, F:]
+        else:
+            h = _act_ref(z, act)
+        o = h.to(x2.dtype).float() @ w2[e].float()
+        slots[sel] = o if b2 is None else o + b2[e].float()
+    slots, out = slots.view(M, k, D), torch.zeros(M, D, dtype=torch.float32, device=x2.device)
+    for j in range(k):
+        out = out + tw[:, j:j + 1].float() * slots[:, j]
+    return out.to(x2.dtype)
+
+
+@R.register_kernel('moe_ffn', 'hip', dtypes=_HALF)
+def _moe_ffn_hip(x2, ids, tw, w1, w2, b1, b2, act):
+    M, D = x2.shape
+    E, F, k = w2.shape[0], w2.shape[1], ids.shape[1]
+    dev = x2.device
+    out = torch.empty(M, D, dtype=x2.dtype, device=dev)
+    h = torch.empty(M * k, F, dtype=x2.dtype, device=dev)
+    ws = torch.empty(M * k, D, dtype=torch.float32, device=dev)
+    idx = torch.empty(E + 1 + 2 * M * k, dtype=torch.int32, device=dev)
+    _native.lib().moe_ffn(_ptr(x2), _ptr(ids), _ptr(tw), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(out),
+                          _ptr(h), _ptr(ws), _ptr(idx), M, D, F, E, k, act, _dt(x2), _stream())
+    return out
+
+
+def moe_ffn(x, ids, weights, w1, w2, b1=None, b2=None, act='swiglu'):
+    """The routed expert FFN of ``x`` [..., D] -> [..., D]: token m is
+    ``sum_j weights[m, j] * (act(x[m] @ w1[e] + b1[e]) @ w2[e] + b2[e])`` over ``e = ids[m, j]``,
+    with ``(ids, weights)`` [M, k] as ``moe_route`` returns them (an expert at most once per
+    token). ``w1`` is [E, D, 2F] for ``act='swiglu'`` (``silu(first half) * second half``) and
+    [E, D, F] for ``'gelu'`` (erf) / ``'relu'``; ``w2`` is [E, F, D]; ``b1`` [E, N1] and ``b2``
+    [E, D] are optional and cast to the dtype of ``x``.
+
+    ``ops/csrc/moe_ffn.hip`` reads only the chosen experts' weights, once, without a host sync (the
+    call can be captured into a graph). It takes bf16 / f16 ``x`` on the GPU with at most
+    ``MOE_MAX_ROWS`` rows, E <= 256, k <= 8, D % 64 == 0 and F % 64 == 0; anything else runs the
+    ``'ref'`` kernel, counted in ``registry.stats()`` as ``('moe_ffn', 'ref')``."""
+    x, ids, weights, w1, w2, b1, b2 = (getattr(t, '_t', t) for t in (x, ids, weights, w1, w2, b1, b2))
+    if act not in _MOE_ACT:
+        raise ValueError(f"moe_ffn: act must be one of {sorted(_MOE_ACT)}, got {act!r}")
+    D = x.shape[-1]
+    x2 = x.reshape(-1, D)
+    M = x2.shape[0]
+    if w2.dim() != 3 or w1.dim() != 3:
+        raise ValueError(f"moe_ffn: w1 / w2 must be [E, D, N1] / [E, F, D], got {tuple(w1.shape)} / "
+                         f"{tuple(w2.shape)}")
+    E, F = w2.shape[0], w2.shape[1]
+    N1 = 2 * F if act == 'swiglu' else F
+    if tuple(w1.shape) != (E, D, N1) or w2.shape[2] != D:
+        raise ValueError(f"moe_ffn: act = {act!r} over x {tuple(x.shape)} needs w1 [E, {D}, N1] and w2 [E, F, {D}] "
+                         f"with N1 = {'2F' if act == 'swiglu' else 'F'}, got w1 {tuple(w1.shape)} and w2 "
+                         f"{tuple(w2.shape)}")
+    if ids.dim() != 2 or ids.shape[0] != M or tuple(weights.shape) != tuple(ids.shape) or ids.shape[1] > E:
+        raise ValueError(f"moe_ffn: ids / weights must be [M = {M}, k <= E = {E}], got {tuple(ids.shape)} / "
+                         f"{tuple(weights.shape)}")
+    for name, b, n in (('b1', b1, N1), ('b2', b2, D)):
+        if b is not None and b.numel() != E * n:
+            raise ValueError(f"moe_ffn: {name} {tuple(b.shape)} has {b.numel()} values for [E = {E}, {n}]")
+    _check_dtypes('moe_ffn', (x, w1), (x, w2))
+    b1 = None if b1 is None else b1.reshape(E, N1).to(x.dtype).contiguous()
+    b2 = None if b2 is None else b2.reshape(E, D).to(x.dtype).contiguous()
+    a = _MOE_ACT[act]
+    if _moe_in_limits(x2, E, ids.shape[1], D, F):
+        y = R.dispatch('moe_ffn', x2, _aligned(x2), ids.to(torch.int32).contiguous(),
+                       weights.float().contiguous(), w1.contiguous(), w2.contiguous(), b1, b2, a)
+    else:
+        R._STATS[('moe_ffn', 'ref')] += 1
+        y = _moe_ffn_ref(x2, ids, weights, w1, w2, b1, b2, a)
+    return y.view(x.shape)

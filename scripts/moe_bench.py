@@ -1,0 +1,94 @@
+"""Top-k routed MoE FFN at decode sizes on the GPU: the moe_ffn.hip kernels against the 'ref'
+composition and a byte floor.
+
+    python scripts/moe_bench.py [--quick] [--samples 5]
+
+Cells: M = 8 and 32 tokens; E = 8 top-2 and E = 64 top-8; D = 2048; F = 1024 and 8192; SwiGLU; bf16.
+Three figures per cell:
+  hip    ``moe_route`` + ``moe_ffn`` on the 'hip' kernels, replayed from a HIP graph that walks over
+         enough copies of the expert weights to exceed the 256 MB last-level cache, so every replay
+         streams the selected experts from HBM as a decode step over a whole model does;
+  ref    the 'ref' composition (fp32 products, a Python loop over the selected experts) on the same
+         GPU and the same copies. It reads the routing on the host, so it cannot be captured and is
+         timed eagerly between two events;
+  floor  the bytes of the experts actually selected (W1 and W2 of every expert some token chose) over
+         the 5.4 TB/s the decode-attention kernel reaches, the HBM rate this project has measured.
+The two variants alternate inside each sample. One JSON line per cell; no GPU is an error, not a
+fallback."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from bench_weight_only import ATTN_TBS, CACHE_BYTES, _graph, _stats, _time  # noqa: E402
+
+
+def cell(M, E, k, D, F, quick, samples):
+    from paddle_ray_amd.ops import fused as K
+    from paddle_ray_amd.ops import registry as R
+    dt, dev = torch.bfloat16, 'cuda'
+    torch.manual_seed(M + E + F)
+    x = torch.randn(M, D, device=dev).to(dt)
+    gw = torch.randn(D, E, device=dev) * D ** -0.5
+    per_expert = 3 * D * F * 2                                   # W1 [D, 2F] + W2 [F, D], bf16
+    copies = 2 if quick else max(1, -(-CACHE_BYTES // (E * per_expert)))
+    ws = [(torch.empty(E, D, 2 * F, device=dev, dtype=dt).normal_(0, D ** -0.5),
+           torch.empty(E, F, D, device=dev, dtype=dt).normal_(0, F ** -0.5)) for _ in range(copies)]
+
+    def hip():
+        for w1, w2 in ws:
+            ids, w = K.moe_route(x, gw, k)
+            y = K.moe_ffn(x, ids, w, w1, w2)
+        return y
+
+    def ref():
+        for w1, w2 in ws:
+            ids, w = K._moe_route_ref(x, gw, k, True)
+            y = K._moe_ffn_ref(x, ids, w, w1, w2, None, None, 4)
+        return y
+
+    R.reset_stats()
+    with torch.no_grad():
+        graph = _graph(hip)
+        assert R.stats() == {('moe_route', 'hip'): 2 * copies, ('moe_ffn', 'hip'): 2 * copies}, R.stats()
+        err = float((hip().float() - ref().float()).abs().max())
+        active = int(K.moe_route(x, gw, k)[0].unique().numel())
+        times = {'hip': [], 'ref': []}
+        for _ in range(samples):
+            times['hip'].append(_time(graph.replay, 2 if quick else 10) / copies)
+            times['ref'].append(_time(ref, 1 if quick else 3) / copies)
+    hip_us, ref_us = _stats(times['hip'], 1e6), _stats(times['ref'], 1e6)
+    floor_us = active * per_expert / (ATTN_TBS * 1e12) * 1e6
+    print(json.dumps(dict(M=M, E=E, top_k=k, D=D, F=F, active_experts=active, weight_copies=copies,
+                          selected_bytes=active * per_expert, hip_us=hip_us, ref_us=ref_us,
+                          floor_us=round(floor_us, 2), hip_over_floor=round(hip_us['median'] / floor_us, 2),
+                          ref_over_hip=round(ref_us['median'] / hip_us['median'], 2),
+                          max_abs_diff_hip_ref=round(err, 5))), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--quick', action='store_true', help='small cells, two copies: a rehearsal, not a measurement')
+    ap.add_argument('--samples', type=int, default=5)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("moe_bench: no GPU (the measurement does not fall back to the CPU)")
+    from paddle_ray_amd.ops import _native
+    _native.require()
+    for E, k in ((8, 2), (64, 8)):
+        for F in (1024, 8192):
+            for M in (8, 32):
+                if a.quick:
+                    cell(M, E, k, 256, F // 8, True, 1)
+                else:
+                    cell(M, E, k, 2048, F, False, a.samples)
+                torch.cuda.empty_cache()
+
+
+if __name__ == '__main__':
+    main()
