@@ -549,8 +549,9 @@ def fused_moe(x, gate_weight, ffn1_weight, ffn2_weight, ffn1_bias=None, ffn1_sca
     ``x`` [B, S, D]; ``gate_weight`` fp32 [D, E]; ``ffn1_weight`` [E, D, N1]; ``ffn2_weight``
     [E, F, D]; biases [E, 1, N1] / [E, 1, D]. The activation follows the weights: N1 == 2F is
     SwiGLU, N1 == F is GELU. Each token goes through its ``moe_topk`` best experts only
-    (``ops.fused.moe_route`` / ``moe_ffn``; at decode sizes on the GPU the kernels of
-    ``ops/csrc/moe_ffn.hip``). Quantised expert weights are not implemented."""
+    (``ops.fused.moe_route`` / ``moe_ffn``; on the GPU the kernels of ``ops/csrc/moe_ffn.hip`` up to
+    64 tokens and the tiled ones of ``ops/csrc/moe_tall.hip`` above, so a prompt stays on HIP and can
+    be captured into a graph like a decode step). Quantised expert weights are not implemented."""
     if quant_method != 'None' or ffn1_scale is not None or ffn2_scale is not None:
         raise NotImplementedError(f"fused_moe: quantised expert weights (quant_method = {quant_method!r}, "
                                   "ffn1_scale / ffn2_scale) are not implemented")

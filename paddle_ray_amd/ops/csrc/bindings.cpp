@@ -126,13 +126,18 @@ PYBIND11_MODULE(_pra_hip, m) {
   Launch<&pra_wo_gemm>::def(m, "wo_gemm",
                             "M outside [1, 64], N % 16, K % 64, K % group_size, or an unsupported group size / "
                             "activation / dtype / split count");
-  // top-k routed mixture-of-experts FFN for at most 64 tokens (contracts above the definitions in moe_ffn.hip)
+  // top-k routed mixture-of-experts FFN: the gate for any M, the skinny products for at most 64 tokens
+  // (contracts above the definitions in moe_ffn.hip) and the tiled products for at most 16384 (token,
+  // slot) pairs (moe_tall.hip)
   Launch<&pra_moe_route>::def(m, "moe_route",
-                              "M outside [1, 64], E outside [1, 256], k outside [1, min(8, E)], D % 64, or an "
+                              "M outside [1, 2^27], E outside [1, 256], k outside [1, min(8, E)], D % 64, or an "
                               "unsupported dtype");
   Launch<&pra_moe_ffn>::def(m, "moe_ffn",
                             "M outside [1, 64], E outside [1, 256], k outside [1, min(8, E)], D % 64, F % 64, or an "
                             "unsupported activation / dtype");
+  Launch<&pra_moe_ffn_tall>::def(m, "moe_ffn_tall",
+                                 "M * k outside [1, 16384], E outside [1, 256], k outside [1, min(8, E)], D % 64, "
+                                 "F % 64, or an unsupported activation / dtype");
   Launch<&pra_bias_gelu_fwd>::def(m, "bias_gelu_fwd");
   Launch<&pra_bias_gelu_bwd>::def(m, "bias_gelu_bwd");
   Launch<&pra_bias_gelu_bwd_db>::def(m, "bias_gelu_bwd_db");

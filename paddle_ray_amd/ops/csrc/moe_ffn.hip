@@ -57,24 +57,15 @@
 // slabs x active experts; a split (with a slice reduction in moe_combine) is future work for small
 // F with few active experts. ids handed to moe_ffn must name an expert at most once per token (what
 // moe_route returns); rows of an expert past 64 would be left uncomputed, never out of bounds.
-#include "common.h"
+#include "moe_common.h"
 #include "pra_api.h"
 
 namespace pra {
 namespace moe {
 
-constexpr int kThreads = 256;
-constexpr int kMaxRows = 64, kMaxExperts = 256, kMaxTopK = 8;
-constexpr int kGelu = 1, kRelu = 3, kSwiglu = 4;   // ops/fused.py _ACT and _MOE_ACT; 0 = the fp32 store
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+constexpr int kMaxRows = 64;
 typedef short v4i16 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
-
-template <typename T> struct V8;
-template <> struct V8<bf16> { typedef __bf16 type __attribute__((ext_vector_type(8))); };
-template <> struct V8<f16> { typedef _Float16 type __attribute__((ext_vector_type(8))); };
 
 template <typename T>
 __device__ __forceinline__ f32x4 mma(typename V8<T>::type a, typename V8<T>::type b, f32x4 c);
@@ -84,31 +75,6 @@ template <> __device__ __forceinline__ f32x4 mma<bf16>(V8<bf16>::type a, V8<bf16
 template <> __device__ __forceinline__ f32x4 mma<f16>(V8<f16>::type a, V8<f16>::type b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
-
-template <typename T> __device__ __forceinline__ uint32_t pack2(float a, float b);
-template <> __device__ __forceinline__ uint32_t pack2<bf16>(float a, float b) { return pack_bf2(a, b); }
-template <> __device__ __forceinline__ uint32_t pack2<f16>(float a, float b) {
-  return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)a) |
-         ((uint32_t)__builtin_bit_cast(uint16_t, (_Float16)b) << 16);
-}
-template <typename T> __device__ __forceinline__ float to_f32(uint16_t u);
-template <> __device__ __forceinline__ float to_f32<bf16>(uint16_t u) { return bf2f(u); }
-template <> __device__ __forceinline__ float to_f32<f16>(uint16_t u) { return (float)__builtin_bit_cast(_Float16, u); }
-
-// 4 consecutive 16-bit values (8-byte aligned) -> fp32
-template <typename T> __device__ __forceinline__ f32x4 load4(const uint16_t* p) {
-  const u32x2 u = *reinterpret_cast<const u32x2*>(p);
-  return f32x4{to_f32<T>((uint16_t)(u[0] & 0xffffu)), to_f32<T>((uint16_t)(u[0] >> 16)),
-               to_f32<T>((uint16_t)(u[1] & 0xffffu)), to_f32<T>((uint16_t)(u[1] >> 16))};
-}
-template <typename T> __device__ __forceinline__ void store4(uint16_t* p, const float* o) {
-  u32x2 u;
-  u[0] = pack2<T>(o[0], o[1]);
-  u[1] = pack2<T>(o[2], o[3]);
-  *reinterpret_cast<u32x2*>(p) = u;
-}
-
-__device__ __forceinline__ int clamp_id(int id, int E) { return min(max(id, 0), E - 1); }
 
 // ---------------------------------------------------------------------------------------- route
 template <typename T>
@@ -333,33 +299,6 @@ __global__ __launch_bounds__(kThreads) void moe_gemm_kernel(const uint16_t* __re
   }
 }
 
-// ---------------------------------------------------------------------------------------- combine
-template <typename T>
-__global__ __launch_bounds__(kThreads) void moe_combine_kernel(const float* __restrict__ ws,
-                                                               const int* __restrict__ pos,
-                                                               const int* __restrict__ ids,
-                                                               const float* __restrict__ tw,
-                                                               const uint16_t* __restrict__ b2,
-                                                               uint16_t* __restrict__ out, int D, int E, int k) {
-  const int m = blockIdx.x;
-  for (int d = threadIdx.x * 4; d < D; d += kThreads * 4) {
-    float o[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int j = 0; j < k; ++j) {
-      const int p = m * k + j;
-      const float wj = tw[p];
-      f32x4 v = *reinterpret_cast<const f32x4*>(ws + (size_t)pos[p] * D + d);
-      if (b2) {
-        const f32x4 b = load4<T>(b2 + (size_t)clamp_id(ids[p], E) * D + d);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] += b[i];
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) o[i] = fmaf(wj, v[i], o[i]);
-    }
-    store4<T>(out + (size_t)m * D + d, o);
-  }
-}
-
 template <typename T, int EPI>
 void launch_gemm(int mb, dim3 grid, hipStream_t s, const uint16_t* a, const uint16_t* w, const uint16_t* bias,
                  const int* off, const int* sorted, int topk, uint16_t* h, float* ws, int K, int N, int NT) {
@@ -399,11 +338,6 @@ void launch_ffn(const void* x, const int* ids, const float* tw, const void* w1, 
                      static_cast<const uint16_t*>(b2), static_cast<uint16_t*>(out), D, E, k);
 }
 
-__host__ bool limits_ok(int M, int D, int E, int k) {
-  return M >= 1 && M <= kMaxRows && E >= 1 && E <= kMaxExperts && k >= 1 && k <= kMaxTopK && k <= E && D >= 64 &&
-         D % 64 == 0;
-}
-
 }  // namespace moe
 }  // namespace pra
 
@@ -411,11 +345,12 @@ extern "C" {
 
 // ids[M, k] (int32) and tw[M, k] (fp32) of x[M, D] (`dt`, f16 / bf16) under gate_weight[D, E] (fp32):
 // the k largest logits in the order of a stable descending sort, softmax over all E at those, divided
-// by their own sum when norm != 0. Returns non-zero without launching for M outside [1, 64], E outside
-// [1, 256], k outside [1, min(8, E)], D % 64, another dt or a missing pointer.
+// by their own sum when norm != 0. One workgroup per token, so any M whose M * k indexes as an int:
+// returns non-zero without launching for M outside [1, 2^27], E outside [1, 256], k outside
+// [1, min(8, E)], D % 64, another dt or a missing pointer.
 int pra_moe_route(const void* x, const float* gate_weight, int* ids, float* tw, int M, int D, int E, int k, int norm,
                   int dt, hipStream_t s) {
-  if (!pra::moe::limits_ok(M, D, E, k) || !x || !gate_weight || !ids || !tw) return 1;
+  if (!pra::moe::limits_ok(M, D, E, k) || M > (1 << 27) || !x || !gate_weight || !ids || !tw) return 1;
   const uint16_t* xp = static_cast<const uint16_t*>(x);
   if (dt == pra::kBF16)
     hipLaunchKernelGGL((pra::moe::moe_route_kernel<pra::bf16>), dim3(M), dim3(pra::moe::kThreads), 0, s, xp,
@@ -432,11 +367,11 @@ int pra_moe_route(const void* x, const float* gate_weight, int* ids, float* tw, 
 // aligned; ids / tw [M, k] as pra_moe_route returns them (an id outside [0, E) is clamped); act 1 erf
 // GELU, 3 ReLU (N1 = F), 4 SwiGLU (N1 = 2F). Workspaces, all written before they are read: h holds
 // M*k*F values of dt, ws M*k*D floats, idx E + 1 + 2*M*k ints. Returns non-zero without launching
-// for the limits of pra_moe_route, F % 64, another act / dt or a missing pointer.
+// for M > 64, the other limits of pra_moe_route, F % 64, another act / dt or a missing pointer.
 int pra_moe_ffn(const void* x, const int* ids, const float* tw, const void* w1, const void* b1, const void* w2,
                 const void* b2, void* out, void* h, float* ws, int* idx, int M, int D, int F, int E, int k, int act,
                 int dt, hipStream_t s) {
-  if (!pra::moe::limits_ok(M, D, E, k) || F < 64 || F % 64) return 1;
+  if (!pra::moe::limits_ok(M, D, E, k) || M > pra::moe::kMaxRows || F < 64 || F % 64) return 1;
   if (act != pra::moe::kGelu && act != pra::moe::kRelu && act != pra::moe::kSwiglu) return 1;
   if (!x || !ids || !tw || !w1 || !w2 || !out || !h || !ws || !idx) return 1;
   if (dt == pra::kBF16)

@@ -4646,10 +4646,11 @@ def weight_only_linear(x, qweight, scale, bias=None, act=None, weight_dtype='int
 
 
 # =============================================================================
-# Top-k routed mixture-of-experts FFN for decode steps (moe_ffn.hip). Parity: the reference's
-# python/paddle/incubate/nn/functional/fused_moe.py.
+# Top-k routed mixture-of-experts FFN: decode steps (moe_ffn.hip) and prefill sizes (moe_tall.hip).
+# Parity: the reference's python/paddle/incubate/nn/functional/fused_moe.py.
 # =============================================================================
-MOE_MAX_ROWS = 64        # tokens the HIP kernels take; taller inputs (prefill) run the ref kernels
+MOE_MAX_ROWS = 64        # tokens the skinny kernels of moe_ffn.hip take; taller inputs run moe_tall.hip
+MOE_MAX_PAIRS = 16384    # (token, slot) pairs one call of moe_tall.hip takes; more tokens go in row chunks
 MOE_MAX_EXPERTS = 256
 MOE_MAX_TOPK = 8
 _MOE_ACT = {'gelu': 1, 'relu': 3, 'swiglu': 4}
@@ -4667,7 +4668,7 @@ def _moe_route_check(x, gate_weight, top_k):
 
 
 def _moe_in_limits(x2, E, k, *dims):
-    return (x2.is_cuda and x2.dtype in _HALF and 1 <= x2.shape[0] <= MOE_MAX_ROWS and E <= MOE_MAX_EXPERTS
+    return (x2.is_cuda and x2.dtype in _HALF and x2.shape[0] >= 1 and E <= MOE_MAX_EXPERTS
             and k <= MOE_MAX_TOPK and all(d % 64 == 0 for d in dims))
 
 
@@ -4708,9 +4709,9 @@ def moe_route(x, gate_weight, top_k, norm_topk_prob=True):
     sort (ties to the lower expert); the weights are ``softmax(logits)`` over all E experts at
     the winners, divided by their own sum (added in slot order) with ``norm_topk_prob``.
 
-    ``ops/csrc/moe_ffn.hip`` takes bf16 / f16 tokens on the GPU with at most ``MOE_MAX_ROWS`` rows,
-    E <= 256, top_k <= 8 and D % 64 == 0; anything else runs the ``'ref'`` kernel, counted in
-    ``registry.stats()`` as ``('moe_route', 'ref')``."""
+    The gate kernel of ``ops/csrc/moe_ffn.hip`` (one workgroup per token) takes bf16 / f16 tokens on
+    the GPU, any number of them, with E <= 256, top_k <= 8 and D % 64 == 0; anything else runs the
+    ``'ref'`` kernel, counted in ``registry.stats()`` as ``('moe_route', 'ref')``."""
     x, gate_weight = getattr(x, '_t', x), getattr(gate_weight, '_t', gate_weight)
     E, k = _moe_route_check(x, gate_weight, top_k)
     x2 = x.reshape(-1, x.shape[-1])
@@ -4751,11 +4752,24 @@ def _moe_ffn_hip(x2, ids, tw, w1, w2, b1, b2, act):
     E, F, k = w2.shape[0], w2.shape[1], ids.shape[1]
     dev = x2.device
     out = torch.empty(M, D, dtype=x2.dtype, device=dev)
-    h = torch.empty(M * k, F, dtype=x2.dtype, device=dev)
-    ws = torch.empty(M * k, D, dtype=torch.float32, device=dev)
-    idx = torch.empty(E + 1 + 2 * M * k, dtype=torch.int32, device=dev)
-    _native.lib().moe_ffn(_ptr(x2), _ptr(ids), _ptr(tw), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(out),
-                          _ptr(h), _ptr(ws), _ptr(idx), M, D, F, E, k, act, _dt(x2), _stream())
+    rows = M if M <= MOE_MAX_ROWS else min(M, MOE_MAX_PAIRS // k)    # tokens per call
+    P = rows * k
+    h = torch.empty(P, F, dtype=x2.dtype, device=dev)
+    ws = torch.empty(P, D, dtype=torch.float32, device=dev)
+    if M <= MOE_MAX_ROWS:
+        idx = torch.empty(E + 1 + 2 * P, dtype=torch.int32, device=dev)
+        _native.lib().moe_ffn(_ptr(x2), _ptr(ids), _ptr(tw), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(out),
+                              _ptr(h), _ptr(ws), _ptr(idx), M, D, F, E, k, act, _dt(x2), _stream())
+        return out
+    # off, per-block histogram, sorted, pos, row-tile table and its count (contract of pra_moe_ffn_tall).
+    # Tokens are independent, so a taller input is a plain loop over row chunks on the same
+    # workspaces: the stream orders the calls, nothing is read back.
+    idx = torch.empty(E + 1 + -(-P // 1024) * E + 2 * P + 3 * (P // 128 + E) + 1, dtype=torch.int32, device=dev)
+    for r0 in range(0, M, rows):
+        n = min(rows, M - r0)
+        _native.lib().moe_ffn_tall(_ptr(x2[r0:]), _ptr(ids[r0:]), _ptr(tw[r0:]), _ptr(w1), _ptr(b1), _ptr(w2),
+                                   _ptr(b2), _ptr(out[r0:]), _ptr(h), _ptr(ws), _ptr(idx), n, D, F, E, k, act,
+                                   _dt(x2), _stream())
     return out
 
 
@@ -4767,10 +4781,13 @@ def moe_ffn(x, ids, weights, w1, w2, b1=None, b2=None, act='swiglu'):
     [E, D, F] for ``'gelu'`` (erf) / ``'relu'``; ``w2`` is [E, F, D]; ``b1`` [E, N1] and ``b2``
     [E, D] are optional and cast to the dtype of ``x``.
 
-    ``ops/csrc/moe_ffn.hip`` reads only the chosen experts' weights, once, without a host sync (the
-    call can be captured into a graph). It takes bf16 / f16 ``x`` on the GPU with at most
-    ``MOE_MAX_ROWS`` rows, E <= 256, k <= 8, D % 64 == 0 and F % 64 == 0; anything else runs the
-    ``'ref'`` kernel, counted in ``registry.stats()`` as ``('moe_ffn', 'ref')``."""
+    The HIP kernels take bf16 / f16 ``x`` on the GPU with E <= 256, k <= 8, D % 64 == 0 and
+    F % 64 == 0, without a host sync (the call can be captured into a graph) and bitwise
+    reproducibly. Up to ``MOE_MAX_ROWS`` tokens (decode steps) ``ops/csrc/moe_ffn.hip`` reads only the
+    chosen experts' weights, once; above that (prefill) ``ops/csrc/moe_tall.hip`` sorts the pairs by
+    expert and runs both products as 128 x 128 MFMA tiles over each expert's rows, ``MOE_MAX_PAIRS``
+    (token, slot) pairs per call and more tokens in row chunks. Anything else runs the ``'ref'``
+    kernel, counted in ``registry.stats()`` as ``('moe_ffn', 'ref')``."""
     x, ids, weights, w1, w2, b1, b2 = (getattr(t, '_t', t) for t in (x, ids, weights, w1, w2, b1, b2))
     if act not in _MOE_ACT:
         raise ValueError(f"moe_ffn: act must be one of {sorted(_MOE_ACT)}, got {act!r}")

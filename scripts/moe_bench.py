@@ -1,9 +1,10 @@
 """Top-k routed MoE FFN at decode sizes on the GPU: the moe_ffn.hip kernels against the 'ref'
 composition and a byte floor.
 
-    python scripts/moe_bench.py [--quick] [--samples 5]
+    python scripts/moe_bench.py [--quick] [--samples 5] [--tall]
 
-Cells: M = 8 and 32 tokens; E = 8 top-2 and E = 64 top-8; D = 2048; F = 1024 and 8192; SwiGLU; bf16.
+``--tall`` runs the prefill cells instead (M = 512 and 4096, the moe_tall.hip kernels; see tall_cell).
+Decode cells: M = 8 and 32 tokens; E = 8 top-2 and E = 64 top-8; D = 2048; F = 1024 and 8192; SwiGLU; bf16.
 Three figures per cell:
   hip    ``moe_route`` + ``moe_ffn`` on the 'hip' kernels, replayed from a HIP graph that walks over
          enough copies of the expert weights to exceed the 256 MB last-level cache, so every replay
@@ -71,10 +72,67 @@ def cell(M, E, k, D, F, quick, samples):
                           max_abs_diff_hip_ref=round(err, 5))), flush=True)
 
 
+GEMM_PFS = 1.51          # best bf16 rate of the project's training GEMM (README, MFMA GEMM row), PFLOP/s
+
+
+def tall_cell(M, E, k, D, F, quick, samples):
+    """Prefill sizes (moe_tall.hip): compute-bound, so one copy of the weights and a flop floor.
+    hip = route + moe_ffn from a graph; ref = the 'ref' composition, eager (what ran before the tiled
+    kernels); lib = a host-routed loop of bf16 library products per expert, eager, for information."""
+    from paddle_ray_amd.ops import fused as K
+    from paddle_ray_amd.ops import registry as R
+    dt, dev = torch.bfloat16, 'cuda'
+    torch.manual_seed(M + E + F)
+    x = torch.randn(M, D, device=dev).to(dt)
+    gw = torch.randn(D, E, device=dev) * D ** -0.5
+    w1 = torch.empty(E, D, 2 * F, device=dev, dtype=dt).normal_(0, D ** -0.5)
+    w2 = torch.empty(E, F, D, device=dev, dtype=dt).normal_(0, F ** -0.5)
+
+    def hip():
+        ids, w = K.moe_route(x, gw, k)
+        return K.moe_ffn(x, ids, w, w1, w2)
+
+    def ref():
+        ids, w = K._moe_route_ref(x, gw, k, True)
+        return K._moe_ffn_ref(x, ids, w, w1, w2, None, None, 4)
+
+    def lib():
+        ids, w = K.moe_route(x, gw, k)
+        flat = ids.reshape(-1).long()
+        slots = torch.empty(M * k, D, dtype=dt, device=dev)
+        for e in flat.unique().tolist():
+            sel = (flat == e).nonzero().squeeze(1)
+            z = x[sel // k] @ w1[e]
+            slots[sel] = (torch.nn.functional.silu(z[:, :F]) * z[:, F:]) @ w2[e]
+        return (slots.view(M, k, D).float() * w[..., None]).sum(1).to(dt)
+
+    R.reset_stats()
+    with torch.no_grad():
+        graph = _graph(hip)
+        assert R.stats() == {('moe_route', 'hip'): 2, ('moe_ffn', 'hip'): 2}, R.stats()
+        err = float((hip().float() - ref().float()).abs().max())
+        times = {'hip': [], 'ref': [], 'lib': []}
+        for _ in range(samples):
+            times['hip'].append(_time(graph.replay, 2 if quick else 10))
+            times['ref'].append(_time(ref, 1 if quick else 2))
+            times['lib'].append(_time(lib, 1 if quick else 3))
+    hip_us, ref_us, lib_us = (_stats(times[n], 1e6) for n in ('hip', 'ref', 'lib'))
+    floor_us = 2.0 * M * k * 3 * D * F / (GEMM_PFS * 1e15) * 1e6
+    print(json.dumps(dict(tall=True, M=M, E=E, top_k=k, D=D, F=F, pairs=M * k, hip_us=hip_us, ref_us=ref_us,
+                          lib_us=lib_us, floor_us=round(floor_us, 2),
+                          hip_over_floor=round(hip_us['median'] / floor_us, 2),
+                          hip_over_lib=round(hip_us['median'] / lib_us['median'], 2),
+                          ref_over_hip=round(ref_us['median'] / hip_us['median'], 2),
+                          faster_beyond_spreads=ref_us['median'] - hip_us['median'] >
+                          ref_us['spread'] + hip_us['spread'],
+                          max_abs_diff_hip_ref=round(err, 5))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--quick', action='store_true', help='small cells, two copies: a rehearsal, not a measurement')
     ap.add_argument('--samples', type=int, default=5)
+    ap.add_argument('--tall', action='store_true', help='the prefill cells (M 512 and 4096) instead of the decode ones')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("moe_bench: no GPU (the measurement does not fall back to the CPU)")
@@ -82,7 +140,13 @@ def main():
     _native.require()
     for E, k in ((8, 2), (64, 8)):
         for F in (1024, 8192):
-            for M in (8, 32):
+            for M in (512, 4096) if a.tall else ():
+                if a.quick:
+                    tall_cell(M, E, k, 256, F // 8, True, 1)
+                else:
+                    tall_cell(M, E, k, 2048, F, False, a.samples)
+                torch.cuda.empty_cache()
+            for M in () if a.tall else (8, 32):
                 if a.quick:
                     cell(M, E, k, 256, F // 8, True, 1)
                 else:
