@@ -298,11 +298,16 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
       ``weight_dtype`` ('int8' / 'int4') and ``weight_group_size``, each quantised from the
       ``[K, N]`` orientation of its product (a ``trans_qkvw=True`` qkv weight: the reshaped
       transpose ``[E, 3*H*D]``); the head dim of a quantised qkv weight is taken from the cache or
-      the qkv bias. A decode step of at most ``ops.fused.WO_MAX_ROWS`` rows runs all four products
-      on the weight-only HIP kernel (``ops.fused.weight_only_linear``): the qkv bias and FFN1's
-      bias + activation in its epilogue, the out-projection and FFN2 without bias (the following
-      add_dropout_layer_norm adds theirs). The context phase and taller steps dequantise each
-      weight to the model dtype, layer by layer, and run the floating-point path unchanged.
+      the qkv bias. On the GPU in bf16 / f16, every phase and any number of rows runs all four
+      products on the weight-only HIP kernels (``ops.fused.weight_only_linear``: ``wo_gemm.hip`` up
+      to ``ops.fused.WO_MAX_ROWS`` rows, ``wo_tall.hip`` above), provided every quantised product of
+      the layer has K % 64 == 0 and N % 16 == 0: the qkv bias and FFN1's bias + activation in the
+      kernel's epilogue, the out-projection and FFN2 without bias (the following
+      add_dropout_layer_norm adds theirs), and no weight is dequantised. A decode step of at most
+      ``WO_MAX_ROWS`` rows calls ``weight_only_linear`` in every other case too (the CPU: its
+      ``'ref'`` kernel). Otherwise (the context phase and taller steps on the CPU, in fp32, or with
+      such a shape) each weight is dequantised to the model dtype, layer by layer, and the
+      floating-point path runs unchanged.
     * every residual add + dropout + following LayerNorm is ONE add_dropout_layer_norm
       kernel; FFN1 runs with its bias+activation in the GEMM epilogue.
     Returns ``out`` or ``(out, cache_kvs)`` when caches are given (updated in place)."""
@@ -338,7 +343,10 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
     if any(s is not None for s in wo_lists) and weight_dtype not in ('int8', 'int4'):
         raise ValueError(f"fused_multi_transformer: weight scales need weight_dtype 'int8' or 'int4', "
                          f"got {weight_dtype!r}")
-    wo_kernel = decode and B * S <= K.WO_MAX_ROWS      # else: dequantise, then the float path
+    wo_skinny = decode and B * S <= K.WO_MAX_ROWS
+    wo_half = h.is_cuda and h.dtype in (torch.bfloat16, torch.float16) and \
+        (K.WO_DECODER_MAX_ROWS is None or B * S <= K.WO_DECODER_MAX_ROWS)
+    wo_qk = 2 if weight_dtype == 'int4' else 1         # levels per byte of a qweight row
     wo_act = 'gelu' if activation == 'gelu' else activation
 
     def wo_scale(lst, i):
@@ -350,6 +358,15 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
     def wo_float(w, sc):
         return K.weight_dequantize(w, sc, weight_dtype, weight_group_size, h.dtype)
 
+    def wo_fits(i):
+        """Whether every quantised product of layer i has a shape the HIP kernels take."""
+        for ws, ss in zip((qkv_weights, linear_weights, ffn1_weights, ffn2_weights), wo_lists):
+            if wo_scale(ss, i) is not None:
+                q = _u(ws[i])
+                if not K._wo_tiled(q.shape[1] * wo_qk, q.shape[0]):
+                    return False
+        return True
+
     def lnp(lst, i, default):
         return _u(lst[i]) if lst is not None and lst[i] is not None else default
 
@@ -357,6 +374,9 @@ def fused_multi_transformer(x, ln_scales, ln_biases, qkv_weights, qkv_biases, li
     y = K.layer_norm(h, lnp(ln_scales, 0, one_w), lnp(ln_biases, 0, zero_b), epsilon) \
         if pre_layer_norm else h
     for i in range(n):
+        # the weight-only kernels: a decode step of few rows as before (on the CPU that is the 'ref'
+        # kernel), and any phase or height on the GPU; else dequantise, then the float path
+        wo_kernel = wo_skinny or (wo_half and wo_fits(i))
         qb = _t(qkv_biases[i]) if qkv_biases else None
         wq, tq, sq = _u(qkv_weights[i]), trans_qkvw, wo_scale(qkv_weight_scales, i)
         if sq is not None:                           # qweight [3*H*D (or (H + 2*KVH)*D), E]

@@ -310,11 +310,14 @@ class FusedMultiTransformerDecoder:
     scale per output channel, or 64 / 128) quantises the model's qkv, out-projection, FFN1 and FFN2
     weights once, here (``paddle.nn.quant.weight_quantize`` of each product's ``[K, N]``
     orientation; kept in ``self.wo_weights``), and never reads the floating weights again: half or
-    a quarter of the bytes a decode step streams and of the memory the weights occupy. ``step`` and
-    ``step_multi`` run the four products on the weight-only HIP kernel inside the captured graphs
-    (``ops.fused.weight_only_linear``, at most ``ops.fused.WO_MAX_ROWS`` = B * T rows); ``prefill``
-    and ``admit`` dequantise each weight per layer and run the floating-point path. Only the linear
-    products differ: every mode above composes with it.
+    a quarter of the bytes a decode step streams and of the memory the weights occupy. On the GPU
+    in bf16 / f16 every call runs the four products on the weight-only HIP kernels
+    (``ops.fused.weight_only_linear``): ``step`` and ``step_multi`` inside the captured graphs
+    (the skinny kernel up to ``ops.fused.WO_MAX_ROWS`` = B * T rows), ``prefill``, ``admit`` and
+    ``extend`` on the tiled kernel once they pass that many rows, so no call rebuilds a
+    floating-point weight. On the CPU, in fp32, or with a product whose K % 64 or N % 16 is not 0,
+    ``prefill``, ``admit`` and taller steps dequantise each weight per layer and run the
+    floating-point path. Only the linear products differ: every mode above composes with it.
     """
 
     def __init__(self, model, batch_size, max_seq_len, use_graph=True, kv_cache_dtype=None,
@@ -729,7 +732,8 @@ class FusedMultiTransformerDecoder:
         graphs alone. Paged mode first allocates the blocks covering [p, p + n_b) of every slot and
         raises ``RuntimeError`` before it changes anything when the free list is short; without
         paging one sync reads the positions to check the room. With ``weight_only`` a chunk of more
-        than ``ops.fused.WO_MAX_ROWS`` rows takes the dequantise-then-float products. Dynamic int8
+        than ``ops.fused.WO_MAX_ROWS`` rows runs the tiled weight-only kernel on the GPU (bf16 /
+        f16) and the dequantise-then-float products elsewhere. Dynamic int8
         scales are the slot's existing ones (later tokens saturate, as in ``step``); a slot whose
         scales were never set by ``prefill`` / ``admit`` raises."""
         import torch

@@ -34,8 +34,9 @@ def weight_dequantize(x, scale, algo='weight_only_int8', out_dtype='float16', gr
 
 def weight_only_linear(x, weight, bias=None, weight_scale=None, weight_dtype='int8', arch=None, group_size=-1):
     """``x @ dequantize(weight, weight_scale) + bias`` for ``x`` [..., K] in bf16 / fp16 (fp32 on the
-    reference path): on the GPU, with at most ``ops.fused.WO_MAX_ROWS`` rows, one HIP kernel that
-    streams the integer weight once (``ops.fused.weight_only_linear``)."""
+    reference path): on the GPU one HIP kernel that never builds the floating-point weight
+    (``ops.fused.weight_only_linear``), streaming the integer weight once up to
+    ``ops.fused.WO_MAX_ROWS`` rows and running 128 x 128 MFMA tiles over the same bytes above."""
     _arch(arch)
     if weight_dtype not in ('int8', 'int4'):
         raise ValueError(f"weight_only_linear: weight_dtype must be 'int8' or 'int4', got {weight_dtype!r}")

@@ -126,6 +126,10 @@ PYBIND11_MODULE(_pra_hip, m) {
   Launch<&pra_wo_gemm>::def(m, "wo_gemm",
                             "M outside [1, 64], N % 16, K % 64, K % group_size, or an unsupported group size / "
                             "activation / dtype / split count");
+  // the same product for any number of rows, tiled (contract above the definition in wo_tall.hip)
+  Launch<&pra_wo_gemm_tall>::def(m, "wo_gemm_tall",
+                                 "M outside [1, 65535 * 128], N % 16, K % 64, K % group_size, or an unsupported "
+                                 "group size / activation / dtype");
   // top-k routed mixture-of-experts FFN: the gate for any M, the skinny products for at most 64 tokens
   // (contracts above the definitions in moe_ffn.hip) and the tiled products for at most 16384 (token,
   // slot) pairs (moe_tall.hip)

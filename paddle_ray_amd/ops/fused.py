@@ -4450,10 +4450,17 @@ def sample_uniform_hip(seed, counter, R, device, step=None):
 
 
 # =============================================================================
-# Weight-only int8 / int4 linear for decode steps (wo_gemm.hip). Parity: the reference's
-# python/paddle/nn/quant/quantized_linear.py weight_quantize / weight_dequantize / weight_only_linear.
+# Weight-only int8 / int4 linear: decode steps (wo_gemm.hip) and taller products (wo_tall.hip).
+# Parity: the reference's python/paddle/nn/quant/quantized_linear.py weight_quantize /
+# weight_dequantize / weight_only_linear.
 # =============================================================================
-WO_MAX_ROWS = 64         # rows of x the HIP kernel takes; taller products run the ref kernel
+WO_MAX_ROWS = 64         # rows of x the skinny kernel of wo_gemm.hip takes; taller products run wo_tall.hip
+WO_TALL_MAX_ROWS = 65535 * 128   # rows one call of wo_tall.hip takes (its grid's y extent); more go in row chunks
+# Rows (B * S) up to which fused_multi_transformer's context phase and taller steps run their
+# weight-only products on the kernels instead of dequantising each weight; None is no limit. The
+# kernels won every measured cell up to 2048 rows (profiles/weight_only_linear.md), so there is none;
+# scripts/bench_weight_only.py sets it to WO_MAX_ROWS to time the dequantising path.
+WO_DECODER_MAX_ROWS = None
 _WO_ALGO = {'weight_only_int8': ('int8', 127.0), 'weight_only_int4': ('int4', 7.0),
             'int8': ('int8', 127.0), 'int4': ('int4', 7.0)}
 
@@ -4600,9 +4607,15 @@ def _wo_hip(x2, qweight, scale, bias, act, wdt, g, splits=None):
     M, K = x2.shape
     N = qweight.shape[0]
     lib = _native.lib()
+    y = torch.empty(M, N, dtype=x2.dtype, device=x2.device)
+    if M > WO_MAX_ROWS:                            # tiled kernel, no split-K; row chunks on the same stream
+        for r0 in range(0, M, WO_TALL_MAX_ROWS):
+            rows = min(WO_TALL_MAX_ROWS, M - r0)
+            lib.wo_gemm_tall(_ptr(x2[r0:r0 + rows]), _ptr(qweight), _ptr(scale), _ptr(bias), _ptr(y[r0:r0 + rows]),
+                             rows, N, K, int(wdt == 'int4'), g, act, _dt(x2), _stream())
+        return y
     most = (K // 64 + 1) // 2
     splits = lib.wo_gemm_splits(M, N, K) if splits is None else max(1, min(int(splits), most))
-    y = torch.empty(M, N, dtype=x2.dtype, device=x2.device)
     ws = torch.empty(splits * M * N, dtype=torch.float32, device=x2.device) if splits > 1 else None
     lib.wo_gemm(_ptr(x2), _ptr(qweight), _ptr(scale), _ptr(bias), _ptr(y), _ptr(ws), M, N, K,
                 int(wdt == 'int4'), g, splits, act, _dt(x2), _stream())
@@ -4611,16 +4624,18 @@ def _wo_hip(x2, qweight, scale, bias, act, wdt, g, splits=None):
 
 def weight_only_linear(x, qweight, scale, bias=None, act=None, weight_dtype='int8', group_size=-1, splits=None):
     """``act(x @ W + bias)`` for ``x`` [..., K] -> [..., N] in the dtype of ``x``, with
-    ``W = weight_dequantize(qweight, scale)`` never materialised on the ``'hip'`` path:
-    ``ops/csrc/wo_gemm.hip`` streams the integer levels once, multiplies them exactly (a level is
-    exact in bf16 / f16) and applies the fp32 scales to fp32 sums, per channel in the epilogue or
-    per group on the group's partial sum. ``act`` is None, ``'gelu'`` (erf) or ``'relu'``;
-    ``bias`` [N] is cast to the dtype of ``x``. ``splits`` overrides the kernel's split-K count
-    (``pra_wo_gemm_splits``); any count gives a bitwise reproducible result.
+    ``W = weight_dequantize(qweight, scale)`` never materialised on the ``'hip'`` path: up to
+    ``WO_MAX_ROWS`` rows ``ops/csrc/wo_gemm.hip`` streams the integer levels once, above that
+    ``ops/csrc/wo_tall.hip`` runs 128 x 128 tiles over the same byte image. Both multiply the levels
+    exactly (a level is exact in bf16 / f16) and apply the fp32 scales to fp32 sums, per channel in
+    the epilogue or per group on the group's partial sum. ``act`` is None, ``'gelu'`` (erf) or
+    ``'relu'``; ``bias`` [N] is cast to the dtype of ``x``. ``splits`` overrides the skinny kernel's
+    split-K count (``pra_wo_gemm_splits``); any count gives a bitwise reproducible result. It has
+    no effect above ``WO_MAX_ROWS`` rows: the tiled kernel does not split K.
 
-    The kernel takes bf16 / f16 ``x`` with at most ``WO_MAX_ROWS`` rows, K % 64 == 0 and
-    N % 16 == 0. Anything else (and the CPU) runs the ``'ref'`` kernel, dequantise then the
-    library product in fp32, counted in ``registry.stats()`` as ``('weight_only_linear', 'ref')``."""
+    The kernels take bf16 / f16 ``x`` with any number of rows >= 1, K % 64 == 0 and N % 16 == 0.
+    Anything else (and the CPU) runs the ``'ref'`` kernel, dequantise then the library product in
+    fp32, counted in ``registry.stats()`` as ``('weight_only_linear', 'ref')``."""
     x, qweight, scale = getattr(x, '_t', x), getattr(qweight, '_t', qweight), getattr(scale, '_t', scale)
     bias = getattr(bias, '_t', bias)
     wdt, _ = _wo_algo(weight_dtype)
@@ -4633,7 +4648,7 @@ def weight_only_linear(x, qweight, scale, bias=None, act=None, weight_dtype='int
         bias = bias.reshape(N).to(x.dtype).contiguous()
     x2 = x.reshape(-1, K)
     a = _ACT[act]
-    if x2.is_cuda and x2.dtype in _HALF and 1 <= x2.shape[0] <= WO_MAX_ROWS and _wo_tiled(K, N):
+    if x2.is_cuda and x2.dtype in _HALF and x2.shape[0] >= 1 and _wo_tiled(K, N):
         x2 = x2.contiguous()
         if x2.data_ptr() % 16:
             x2 = x2.clone()

@@ -1,6 +1,6 @@
 """Weight-only int8 / int4 linear on the GPU against the bf16 library product it replaces.
 
-    python scripts/bench_weight_only.py [--quick] [--sections products,decoder] [--samples 5]
+    python scripts/bench_weight_only.py [--quick] [--sections products,decoder,tall,prefill] [--samples 5]
 
 Part 1 times the four products of a 2048-wide, 8192-FFN transformer layer at M = 8 and 32 rows:
 int8 per channel, int4 per channel and int4 with group 128 on ``ops.fused.weight_only_linear``, and
@@ -11,6 +11,15 @@ over a whole model does. Variants alternate inside each of five samples. Bytes a
 the shapes: the weight image, its scales, x, y and the bias.
 Part 2 times ``step`` and ``step_multi(T = 4)`` of the 24-layer 2048-wide graph decoder of
 ``profiles/decode_multi.md`` with ``weight_only`` None / int8 / int4.
+Section ``tall`` times the same four products at M = 128, 512 and 2048 rows, where the tiled kernel
+of ``wo_tall.hip`` runs, for int8 and int4 with per-channel and group-128 scales, against what the
+call did before that kernel (``ref``: dequantise to fp32 + the fp32 library product), what the
+decoder's prefill did (``dequant+mm``: ``weight_dequantize`` to bf16 + the bf16 library product) and
+the bf16 library product alone on a weight dequantised beforehand (``mm``), the floor for a kernel
+that does the same flops. The weights (at most 32 MB) stay in the last-level cache, as they do
+between the row tiles of a prompt. Section ``prefill`` times ``prefill`` of the 24-layer decoder and
+reads its peak allocated memory with the products on the kernels and with the per-layer dequantised
+copies (``ops.fused.WO_DECODER_MAX_ROWS`` set to ``WO_MAX_ROWS``, the behaviour before wo_tall.hip).
 One JSON line per measurement; no GPU is an error, not a fallback."""
 import argparse
 import json
@@ -145,6 +154,87 @@ def decoder(quick, samples):
                               over_bf16=round(st['median'] / base, 3))), flush=True)
 
 
+def tall(quick, samples):
+    from paddle_ray_amd.ops import fused as K
+    from paddle_ray_amd.ops import registry as R
+    shapes = [('qkv', 2048, 6144, False), ('out', 2048, 2048, False), ('ffn1', 2048, 8192, True),
+              ('ffn2', 8192, 2048, False)]
+    variants = [('int8', 'int8', -1), ('int8 g128', 'int8', 128), ('int4', 'int4', -1), ('int4 g128', 'int4', 128)]
+    gen = torch.Generator().manual_seed(0)
+    for name, Kd, N, epi in shapes[:1] if quick else shapes:
+        w = torch.randn(Kd, N, generator=gen) * 0.05
+        bias = torch.randn(N, generator=gen).bfloat16().cuda() if epi else None
+        act = 'gelu' if epi else None
+        for label, wdt, g in variants[:1] if quick else variants:
+            q, s = (t.cuda() for t in K.weight_quantize(w, wdt, g))
+            wd = K.weight_dequantize(q, s, wdt, g, torch.bfloat16)
+            for M in (128,) if quick else (128, 512, 2048):
+                x = torch.randn(M, Kd, generator=gen).bfloat16().cuda()
+
+                def mm(wd=wd):
+                    return torch.nn.functional.gelu(torch.addmm(bias, x, wd)) if epi else torch.mm(x, wd)
+                paths = {'kernel': lambda: K.weight_only_linear(x, q, s, bias, act, wdt, g),
+                         'ref': lambda: K._wo_ref(x, q, s, bias, K._ACT[act], wdt, g),
+                         'dequant+mm': lambda: mm(K.weight_dequantize(q, s, wdt, g, torch.bfloat16)),
+                         'mm': mm}
+                R.reset_stats()
+                with torch.no_grad():
+                    y, yr = paths['kernel'](), paths['mm']()
+                assert R.stats() == {('weight_only_linear', 'hip'): 1}, R.stats()
+                err = float((y.float() - yr.float()).abs().max() / yr.float().abs().max())
+                times = {k: [] for k in paths}
+                with torch.no_grad():
+                    for _ in range(samples):               # the paths alternate inside a sample
+                        for k, fn in paths.items():
+                            times[k].append(_time(fn, (2 if quick else 5) if k in ('ref', 'dequant+mm') else
+                                                  (5 if quick else 100)))
+                med = {k: statistics.median(v) for k, v in times.items()}
+                for k in paths:
+                    print(json.dumps(dict(section='tall', product=name, K=Kd, N=N, M=M, variant=label, path=k,
+                                          us=_stats(times[k], 1e6),
+                                          tflops=round(2.0 * M * N * Kd / med[k] / 1e12, 1),
+                                          over_mm=round(med[k] / med['mm'], 2),
+                                          kernel_vs_mm_max_rel_diff=round(err, 5))), flush=True)
+
+
+def prefill(quick, samples):
+    import paddle_ray_amd as paddle
+    from paddle_ray_amd.incubate.nn import FusedMultiTransformer, FusedMultiTransformerDecoder
+    from paddle_ray_amd.device import cuda as mem
+    from paddle_ray_amd.ops import fused as K
+    paddle.set_device('gpu')
+    E, H, layers, B = 2048, 16, (2 if quick else 24), 8
+    m = FusedMultiTransformer(E, H, 4 * E, num_layers=layers)
+    m.eval()
+    m.to(dtype='bfloat16')
+    for wo in ('int8', 'int4'):
+        d = FusedMultiTransformerDecoder(m, B, 256 + 8, weight_only=wo, use_graph=False)
+        for S in (64,) if quick else (16, 64, 256):        # 128, 512 and 2048 rows
+            x = paddle.Tensor(torch.randn(B, S, E, device='cuda', dtype=torch.bfloat16))
+            limits = {'kernels': None, 'dequantised copies': K.WO_MAX_ROWS}
+            times, peak = {k: [] for k in limits}, {}
+            try:
+                for _ in range(samples + 1):               # the first round warms up and reads the peaks
+                    for k, lim in limits.items():
+                        K.WO_DECODER_MAX_ROWS = lim
+                        torch.cuda.synchronize()
+                        base = mem.memory_allocated()
+                        mem.reset_max_memory_allocated()
+                        t = _time(lambda: d.prefill(x), 1 if quick else 3)
+                        if k in peak:
+                            times[k].append(t)
+                        peak[k] = mem.max_memory_allocated() - base
+            finally:
+                K.WO_DECODER_MAX_ROWS = None
+            base = statistics.median(times['dequantised copies'])
+            for k in limits:
+                st = _stats(times[k], 1e3)
+                print(json.dumps(dict(section='prefill', model=f'{layers}x{E}', batch=B, S=S, rows=B * S,
+                                      weight_only=wo, products=k, ms=st, peak_mb_above_resident=round(peak[k] / 2**20, 1),
+                                      over_dequantised=round(st['median'] / (base * 1e3), 3))), flush=True)
+        del d
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--quick', action='store_true', help='one product, two layers: a rehearsal, not a measurement')
@@ -159,6 +249,10 @@ def main():
         products(a.quick, a.samples)
     if 'decoder' in a.sections:
         decoder(a.quick, a.samples)
+    if 'tall' in a.sections:
+        tall(a.quick, a.samples)
+    if 'prefill' in a.sections:
+        prefill(a.quick, a.samples)
 
 
 if __name__ == '__main__':
