@@ -563,6 +563,31 @@ def fused_ec_moe(x, gate, bmm0_weight, bmm0_bias, bmm1_weight, bmm1_bias, act_ty
     return Tensor((o * g.unsqueeze(-1)).sum(2))
 
 
+def _fused_moe_wo(x, gate_weight, ffn1_weight, ffn2_weight, ffn1_bias, ffn1_scale, ffn2_bias, ffn2_scale,
+                  quant_method, moe_topk, norm_topk_prob):
+    """fused_moe over weight-only int8 / int4 expert weights: the activation and the group size follow
+    the shapes, everything else is checked by ops.fused.moe_ffn."""
+    t, w1, w2 = _u(x), _u(ffn1_weight), _u(ffn2_weight)
+    if w1.is_floating_point() or w2.is_floating_point():
+        raise NotImplementedError(f"fused_moe: quant_method = {quant_method!r} over {w1.dtype} / {w2.dtype} weights: "
+                                  "quantising inside the call is not implemented, pass the (qweight, scale) pairs "
+                                  "of ops.fused.weight_quantize")
+    s1 = None if ffn1_scale is None else _u(ffn1_scale)
+    s2 = None if ffn2_scale is None else _u(ffn2_scale)
+    pk = 2 if quant_method == 'weight_only_int4' else 1
+    if w1.dim() != 3 or w2.dim() != 3 or w1.shape[1] not in (w2.shape[2] * pk, 2 * w2.shape[2] * pk):
+        raise ValueError(f"fused_moe: {quant_method} ffn1_weight [E, F or 2F, D{' / 2' if pk == 2 else ''}] / "
+                         f"ffn2_weight [E, D, F{' / 2' if pk == 2 else ''}] expected, got {tuple(w1.shape)} / "
+                         f"{tuple(w2.shape)}")
+    act = 'swiglu' if w1.shape[1] == 2 * w2.shape[2] * pk else 'gelu'
+    group = t.shape[-1] // s1.shape[1] if s1 is not None and s1.dim() == 3 and s1.shape[1] > 0 else -1
+    ids, w = K.moe_route(t, _u(gate_weight), moe_topk, norm_topk_prob)
+    b1 = None if ffn1_bias is None else _u(ffn1_bias)
+    b2 = None if ffn2_bias is None else _u(ffn2_bias)
+    return Tensor(K.moe_ffn(t, ids, w, w1, w2, b1, b2, act, w1_scale=s1, w2_scale=s2, weight_dtype=quant_method,
+                            group_size=group))
+
+
 def fused_moe(x, gate_weight, ffn1_weight, ffn2_weight, ffn1_bias=None, ffn1_scale=None, ffn2_bias=None,
               ffn2_scale=None, quant_method='None', moe_topk=2, norm_topk_prob=True):
     """Top-k routed mixture-of-experts FFN (parity: python/paddle/incubate/nn/functional/fused_moe.py).
@@ -571,10 +596,25 @@ def fused_moe(x, gate_weight, ffn1_weight, ffn2_weight, ffn1_bias=None, ffn1_sca
     SwiGLU, N1 == F is GELU. Each token goes through its ``moe_topk`` best experts only
     (``ops.fused.moe_route`` / ``moe_ffn``; on the GPU the kernels of ``ops/csrc/moe_ffn.hip`` up to
     64 tokens and the tiled ones of ``ops/csrc/moe_tall.hip`` above, so a prompt stays on HIP and can
-    be captured into a graph like a decode step). Quantised expert weights are not implemented."""
-    if quant_method != 'None' or ffn1_scale is not None or ffn2_scale is not None:
-        raise NotImplementedError(f"fused_moe: quantised expert weights (quant_method = {quant_method!r}, "
-                                  "ffn1_scale / ffn2_scale) are not implemented")
+    be captured into a graph like a decode step).
+
+    Weight-only quantised experts: with ``quant_method`` ``'weight_only_int8'`` /
+    ``'weight_only_int4'`` the weights are the int8 tensors ``ops.fused.weight_quantize`` returns
+    for the stacked weights above, ``ffn1_weight`` [E, N1, D] and ``ffn2_weight`` [E, D, F] (the last
+    dimension halved for int4), with their fp32 scales ``ffn1_scale`` / ``ffn2_scale``: [E, N] per
+    channel, or [E, K / g, N] per group, the group size g being ``D // ffn1_scale.shape[1]``. They run
+    ``ops/csrc/moe_wo.hip`` (``moe_ffn(..., weight_dtype=...)``; above 64 tokens in chunks of 64).
+    Quantising inside the call, scales under ``quant_method='None'`` and any other scheme are not
+    implemented."""
+    if quant_method in ('weight_only_int8', 'weight_only_int4'):
+        return _fused_moe_wo(x, gate_weight, ffn1_weight, ffn2_weight, ffn1_bias, ffn1_scale, ffn2_bias, ffn2_scale,
+                             quant_method, moe_topk, norm_topk_prob)
+    if quant_method != 'None':
+        raise NotImplementedError(f"fused_moe: quant_method = {quant_method!r} is not implemented ('None', "
+                                  "'weight_only_int8' and 'weight_only_int4' are)")
+    if ffn1_scale is not None or ffn2_scale is not None:
+        raise NotImplementedError("fused_moe: ffn1_scale / ffn2_scale under quant_method = 'None' are a scheme that "
+                                  "is not implemented")
     t, w1, w2 = _u(x), _u(ffn1_weight), _u(ffn2_weight)
     if w1.dim() != 3 or w2.dim() != 3 or w1.shape[-1] not in (w2.shape[1], 2 * w2.shape[1]):
         raise ValueError(f"fused_moe: ffn1_weight [E, D, F or 2F] / ffn2_weight [E, F, D] expected, got "

@@ -92,10 +92,11 @@ _HIP_FLAGS = ('-O3', '-fPIC', '-std=c++17', '-munsafe-fp-atomics')
 # profiles/prefill_attn.md is of the build with the flag, the packed build was never run or timed.
 # moe_ffn.hip is wo_gemm.hip's case again (fp32 vectors in the epilogues and the combine); it too was
 # only ever built, tested and timed with the flag, and so were moe_tall.hip (the same epilogues) and
-# wo_tall.hip (wo_gemm.hip's epilogue and group-scale updates).
+# wo_tall.hip (wo_gemm.hip's epilogue and group-scale updates) and moe_wo.hip (both of those over
+# expert weights).
 _NO_PK_F32 = ('-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops')
 _EXTRA_FLAGS = {'wo_gemm.hip': _NO_PK_F32, 'prefill_attn.hip': _NO_PK_F32, 'moe_ffn.hip': _NO_PK_F32,
-                'moe_tall.hip': _NO_PK_F32, 'wo_tall.hip': _NO_PK_F32}
+                'moe_tall.hip': _NO_PK_F32, 'wo_tall.hip': _NO_PK_F32, 'moe_wo.hip': _NO_PK_F32}
 
 
 def _toolchain_key():

@@ -142,6 +142,11 @@ PYBIND11_MODULE(_pra_hip, m) {
   Launch<&pra_moe_ffn_tall>::def(m, "moe_ffn_tall",
                                  "M * k outside [1, 16384], E outside [1, 256], k outside [1, min(8, E)], D % 64, "
                                  "F % 64, or an unsupported activation / dtype");
+  // the skinny products over weight-only int8 / int4 expert weights (contract above the definition in
+  // moe_wo.hip)
+  Launch<&pra_moe_ffn_wo>::def(m, "moe_ffn_wo",
+                               "M outside [1, 64], E outside [1, 256], k outside [1, min(8, E)], D % 64, F % 64, "
+                               "D or F % group_size, or an unsupported group size / activation / dtype");
   Launch<&pra_bias_gelu_fwd>::def(m, "bias_gelu_fwd");
   Launch<&pra_bias_gelu_bwd>::def(m, "bias_gelu_bwd");
   Launch<&pra_bias_gelu_bwd_db>::def(m, "bias_gelu_bwd_db");

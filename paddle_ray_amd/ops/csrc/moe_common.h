@@ -1,6 +1,6 @@
 // What the routed mixture-of-experts kernels share (moe_ffn.hip for decode steps, moe_tall.hip for
-// prefill sizes): limits, activation codes, 16-bit <-> fp32 helpers and the combine kernel that ends
-// both paths.
+// prefill sizes): limits, activation codes, 16-bit <-> fp32 helpers, the index kernel of the skinny paths
+// (moe_ffn.hip, moe_wo.hip) and the combine kernel that ends every path.
 #pragma once
 #include "common.h"
 
@@ -9,6 +9,7 @@ namespace moe {
 
 constexpr int kThreads = 256;
 constexpr int kMaxExperts = 256, kMaxTopK = 8;
+constexpr int kMaxRows = 64;                      // tokens the skinny kernels (moe_ffn.hip, moe_wo.hip) take
 constexpr int kGelu = 1, kRelu = 3, kSwiglu = 4;   // ops/fused.py _ACT and _MOE_ACT; 0 = the fp32 store
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -42,6 +43,47 @@ template <typename T> __device__ __forceinline__ void store4(uint16_t* p, const 
 }
 
 __device__ __forceinline__ int clamp_id(int id, int E) { return min(max(id, 0), E - 1); }
+
+// ---------------------------------------------------------------------------------------- index
+// Counting sort of the P <= MAXP (token, slot) pairs by expert, one workgroup (moe_ffn.hip and moe_wo.hip;
+// the steps are described at the top of moe_ffn.hip). A template so that both files can hold it.
+template <int MAXP>
+__global__ __launch_bounds__(kThreads) void moe_index_kernel(const int* __restrict__ ids, int* __restrict__ off,
+                                                             int* __restrict__ sorted, int* __restrict__ pos, int P,
+                                                             int E) {
+  __shared__ int sid[MAXP];
+  __shared__ int cnt[kMaxExperts + 1];
+  const int tid = threadIdx.x;
+  for (int p = tid; p < P; p += kThreads) sid[p] = clamp_id(ids[p], E);
+  __syncthreads();
+  if (tid < E) {
+    int c = 0;
+    for (int p = 0; p < P; ++p) c += sid[p] == tid ? 1 : 0;
+    cnt[tid] = c;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int run = 0;
+    for (int e = 0; e < E; ++e) {
+      const int c = cnt[e];
+      cnt[e] = run;
+      run += c;
+    }
+    cnt[E] = run;
+  }
+  __syncthreads();
+  for (int i = tid; i <= E; i += kThreads) off[i] = cnt[i];
+  if (tid < E) {
+    int s = cnt[tid];
+    for (int p = 0; p < P; ++p) {
+      if (sid[p] == tid) {
+        sorted[s] = p;
+        pos[p] = s;
+        ++s;
+      }
+    }
+  }
+}
 
 // ---------------------------------------------------------------------------------------- combine
 template <typename T>

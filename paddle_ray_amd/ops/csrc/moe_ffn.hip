@@ -63,7 +63,6 @@
 namespace pra {
 namespace moe {
 
-constexpr int kMaxRows = 64;
 typedef short v4i16 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
 
@@ -140,44 +139,6 @@ __global__ __launch_bounds__(kThreads) void moe_route_kernel(const uint16_t* __r
     }
     ids[m * k + tid] = clamp_id(sel[tid], E);
     tw[m * k + tid] = v;
-  }
-}
-
-// ---------------------------------------------------------------------------------------- index
-__global__ __launch_bounds__(kThreads) void moe_index_kernel(const int* __restrict__ ids, int* __restrict__ off,
-                                                             int* __restrict__ sorted, int* __restrict__ pos, int P,
-                                                             int E) {
-  __shared__ int sid[kMaxRows * kMaxTopK];
-  __shared__ int cnt[kMaxExperts + 1];
-  const int tid = threadIdx.x;
-  for (int p = tid; p < P; p += kThreads) sid[p] = clamp_id(ids[p], E);
-  __syncthreads();
-  if (tid < E) {
-    int c = 0;
-    for (int p = 0; p < P; ++p) c += sid[p] == tid ? 1 : 0;
-    cnt[tid] = c;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    int run = 0;
-    for (int e = 0; e < E; ++e) {
-      const int c = cnt[e];
-      cnt[e] = run;
-      run += c;
-    }
-    cnt[E] = run;
-  }
-  __syncthreads();
-  for (int i = tid; i <= E; i += kThreads) off[i] = cnt[i];
-  if (tid < E) {
-    int s = cnt[tid];
-    for (int p = 0; p < P; ++p) {
-      if (sid[p] == tid) {
-        sorted[s] = p;
-        pos[p] = s;
-        ++s;
-      }
-    }
   }
 }
 
@@ -328,7 +289,7 @@ void launch_ffn(const void* x, const int* ids, const float* tw, const void* w1, 
   const uint16_t* w1p = static_cast<const uint16_t*>(w1);
   const uint16_t* b1p = static_cast<const uint16_t*>(b1);
   uint16_t* hp = static_cast<uint16_t*>(h);
-  hipLaunchKernelGGL(moe_index_kernel, dim3(1), dim3(kThreads), 0, s, ids, off, sorted, pos, P, E);
+  hipLaunchKernelGGL(moe_index_kernel<kMaxRows * kMaxTopK>, dim3(1), dim3(kThreads), 0, s, ids, off, sorted, pos, P, E);
   const dim3 g1(F / 64, E), g2(D / 64, E);
   if (act == kSwiglu) launch_gemm<T, kSwiglu>(mb, g1, s, xp, w1p, b1p, off, sorted, k, hp, nullptr, D, F, 2 * F);
   else if (act == kGelu) launch_gemm<T, kGelu>(mb, g1, s, xp, w1p, b1p, off, sorted, k, hp, nullptr, D, F, F);

@@ -4546,9 +4546,16 @@ def weight_quantize(w, algo='weight_only_int8', group_size=-1):
     byte), with its bytes in the tile order of the HIP kernel (``ops/csrc/wo_gemm.hip``): it is not
     a matrix to index (a shape the kernel does not take, K % 64 or N % 16, keeps plain [N, K]
     rows). The only supported readers are ``weight_dequantize`` and
-    ``weight_only_linear``, called with the same ``algo`` and ``group_size``."""
+    ``weight_only_linear``, called with the same ``algo`` and ``group_size``.
+
+    A ``[E, K, N]`` stack of expert weights gives ``qweight`` ``[E, N, K or K // 2]`` and ``scale``
+    ``[E, N]`` or ``[E, K / group_size, N]``, expert e being exactly what the 2-D call returns for
+    ``w[e]``: the operands of ``moe_ffn(..., weight_dtype=...)``."""
     w = getattr(w, '_t', w)
     wdt, qmax = _wo_algo(algo)
+    if w.dim() == 3 and w.shape[0] > 0 and w.is_floating_point():
+        pairs = [weight_quantize(w[e], algo, group_size) for e in range(w.shape[0])]
+        return torch.stack([q for q, _ in pairs]), torch.stack([s for _, s in pairs])
     if w.dim() != 2 or not w.is_floating_point():
         raise ValueError(f"weight_quantize: w must be a floating-point [K, N] matrix, got {w.dtype} "
                          f"{tuple(w.shape)}")
@@ -4584,9 +4591,14 @@ def _wo_check(qweight, scale, wdt, group_size, K=None):
 
 def weight_dequantize(qweight, scale, algo='weight_only_int8', group_size=-1, out_dtype=torch.float16):
     """``[K, N]`` = level * scale of a ``weight_quantize`` pair, computed in fp32 and cast to
-    ``out_dtype``; with ``torch.float32`` it is the exact inverse of the layout."""
+    ``out_dtype``; with ``torch.float32`` it is the exact inverse of the layout. A stacked pair
+    (``qweight`` [E, N, K or K // 2]) gives ``[E, K, N]``, expert by expert."""
     qweight, scale = getattr(qweight, '_t', qweight), getattr(scale, '_t', scale)
     wdt, _ = _wo_algo(algo)
+    if isinstance(qweight, torch.Tensor) and qweight.dim() == 3 and isinstance(scale, torch.Tensor) \
+            and scale.dim() >= 2 and scale.shape[0] == qweight.shape[0] > 0:
+        return torch.stack([weight_dequantize(qweight[e], scale[e], algo, group_size, out_dtype)
+                            for e in range(qweight.shape[0])])
     K, N, g = _wo_check(qweight, scale, wdt, group_size)
     lv = _wo_unpack(qweight, K, N, wdt).float()
     w = (lv.view(K // g, g, N) * scale[:, None]).view(K, N) if g > 0 else lv * scale
@@ -4788,7 +4800,74 @@ def _moe_ffn_hip(x2, ids, tw, w1, w2, b1, b2, act):
     return out
 
 
-def moe_ffn(x, ids, weights, w1, w2, b1=None, b2=None, act='swiglu'):
+class _DequantisedExperts:
+    """``self[e]`` = expert e of a stacked (qweight, scale) pair as fp32 [K, N]; only the experts
+    that are asked for are dequantised."""
+
+    def __init__(self, qweight, scale, wdt, g):
+        self.qweight, self.scale, self.wdt, self.g = qweight, scale, wdt, g
+
+    def __getitem__(self, e):
+        return weight_dequantize(self.qweight[e], self.scale[e], self.wdt, self.g, torch.float32)
+
+
+@R.register_kernel('moe_ffn_wo', 'ref')
+def _moe_ffn_wo_ref(x2, ids, tw, w1, w2, s1, s2, b1, b2, act, wdt, g):
+    """``_moe_ffn_ref`` over each used expert dequantised to fp32."""
+    return _moe_ffn_ref(x2, ids, tw, _DequantisedExperts(w1, s1, wdt, g), _DequantisedExperts(w2, s2, wdt, g),
+                        b1, b2, act)
+
+
+@R.register_kernel('moe_ffn_wo', 'hip', dtypes=_HALF)
+def _moe_ffn_wo_hip(x2, ids, tw, w1, w2, s1, s2, b1, b2, act, wdt, g):
+    M, D = x2.shape
+    E, k = w2.shape[0], ids.shape[1]
+    F = w2.shape[2] * (2 if wdt == 'int4' else 1)
+    dev = x2.device
+    out = torch.empty(M, D, dtype=x2.dtype, device=dev)
+    rows = min(M, MOE_MAX_ROWS)                    # tokens per call
+    P = rows * k
+    h = torch.empty(P, F, dtype=x2.dtype, device=dev)
+    ws = torch.empty(P, D, dtype=torch.float32, device=dev)
+    idx = torch.empty(E + 1 + 2 * P, dtype=torch.int32, device=dev)
+    # Tokens are independent, so a taller input is a plain loop over chunks of MOE_MAX_ROWS tokens on
+    # the same workspaces: the stream orders the calls, nothing is read back. Every chunk reads the
+    # weights of the experts it chose again.
+    for r0 in range(0, M, rows):
+        _native.lib().moe_ffn_wo(_ptr(x2[r0:]), _ptr(ids[r0:]), _ptr(tw[r0:]), _ptr(w1), _ptr(s1), _ptr(b1),
+                                 _ptr(w2), _ptr(s2), _ptr(b2), _ptr(out[r0:]), _ptr(h), _ptr(ws), _ptr(idx),
+                                 min(rows, M - r0), D, F, E, k, act, int(wdt == 'int4'), g, _dt(x2), _stream())
+    return out
+
+
+def _moe_wo_check(x, w1, w2, w1_scale, w2_scale, act, wdt, group_size):
+    """Shapes of stacked quantised expert weights and their scales -> (E, F, N1, group_size);
+    ValueError with the shapes."""
+    D, pk = x.shape[-1], 2 if wdt == 'int4' else 1
+    for name, w in (('w1', w1), ('w2', w2)):
+        if not isinstance(w, torch.Tensor) or w.dtype != torch.int8 or w.dim() != 3:
+            raise ValueError(f"moe_ffn: a {wdt} {name} must be the stacked int8 tensor weight_quantize returned for "
+                             f"[E, K, N] weights, got {getattr(w, 'dtype', type(w))} "
+                             f"{tuple(getattr(w, 'shape', ()))}")
+    E, F = w2.shape[0], w2.shape[2] * pk
+    N1 = 2 * F if act == 'swiglu' else F
+    if tuple(w1.shape) != (E, N1, D // pk) or w2.shape[1] != D or D % pk:
+        raise ValueError(f"moe_ffn: act = {act!r} over x {tuple(x.shape)} needs {wdt} w1 [E, N1, {D // pk}] and w2 "
+                         f"[E, {D}, F{' / 2' if pk == 2 else ''}] with N1 = {'2F' if act == 'swiglu' else 'F'}, got "
+                         f"w1 {tuple(w1.shape)} and w2 {tuple(w2.shape)}")
+    g = _wo_group(D, group_size, wdt)
+    _wo_group(F, group_size, wdt)
+    for name, s, K, N in (('w1_scale', w1_scale, D, N1), ('w2_scale', w2_scale, F, D)):
+        want = (E, K // g, N) if g > 0 else (E, N)
+        if not isinstance(s, torch.Tensor) or tuple(s.shape) != want or s.dtype != torch.float32:
+            raise ValueError(f"moe_ffn: {name} must be fp32 {want} for {wdt} weights w1 {tuple(w1.shape)} / w2 "
+                             f"{tuple(w2.shape)} (group_size = {g}), got "
+                             f"{(s.dtype, tuple(s.shape)) if isinstance(s, torch.Tensor) else s}")
+    return E, F, N1, g
+
+
+def moe_ffn(x, ids, weights, w1, w2, b1=None, b2=None, act='swiglu', w1_scale=None, w2_scale=None,
+            weight_dtype=None, group_size=-1):
     """The routed expert FFN of ``x`` [..., D] -> [..., D]: token m is
     ``sum_j weights[m, j] * (act(x[m] @ w1[e] + b1[e]) @ w2[e] + b2[e])`` over ``e = ids[m, j]``,
     with ``(ids, weights)`` [M, k] as ``moe_route`` returns them (an expert at most once per
@@ -4802,36 +4881,58 @@ def moe_ffn(x, ids, weights, w1, w2, b1=None, b2=None, act='swiglu'):
     chosen experts' weights, once; above that (prefill) ``ops/csrc/moe_tall.hip`` sorts the pairs by
     expert and runs both products as 128 x 128 MFMA tiles over each expert's rows, ``MOE_MAX_PAIRS``
     (token, slot) pairs per call and more tokens in row chunks. Anything else runs the ``'ref'``
-    kernel, counted in ``registry.stats()`` as ``('moe_ffn', 'ref')``."""
-    x, ids, weights, w1, w2, b1, b2 = (getattr(t, '_t', t) for t in (x, ids, weights, w1, w2, b1, b2))
+    kernel, counted in ``registry.stats()`` as ``('moe_ffn', 'ref')``.
+
+    Weight-only quantised experts: with ``weight_dtype`` ``'int8'`` / ``'int4'``, ``w1`` / ``w2`` are
+    the stacked byte images ``weight_quantize`` returns for the ``[E, D, N1]`` / ``[E, F, D]``
+    weights (int8 ``[E, N1, D]`` / ``[E, D, F]``, the last dimension halved for int4) and
+    ``w1_scale`` / ``w2_scale`` their fp32 scales (``[E, N]``, or ``[E, K / group_size, N]`` for
+    ``group_size`` 64 / 128, which must divide D and F). Within the same limits the registry op
+    ``'moe_ffn_wo'`` runs ``ops/csrc/moe_wo.hip``, which streams the chosen experts' levels once per
+    call of up to ``MOE_MAX_ROWS`` tokens and applies the fp32 scales to fp32 sums. There is no tiled
+    quantised kernel yet: a taller input stays on HIP as a plain loop over chunks of ``MOE_MAX_ROWS``
+    tokens, and every chunk reads the weights of the experts it chose again. The ``'ref'`` kernel
+    dequantises each used expert to fp32 and follows the arithmetic above, counted as
+    ``('moe_ffn_wo', 'ref')``."""
+    x, ids, weights, w1, w2, b1, b2, w1_scale, w2_scale = (getattr(t, '_t', t) for t in
+                                                           (x, ids, weights, w1, w2, b1, b2, w1_scale, w2_scale))
     if act not in _MOE_ACT:
         raise ValueError(f"moe_ffn: act must be one of {sorted(_MOE_ACT)}, got {act!r}")
     D = x.shape[-1]
     x2 = x.reshape(-1, D)
     M = x2.shape[0]
-    if w2.dim() != 3 or w1.dim() != 3:
-        raise ValueError(f"moe_ffn: w1 / w2 must be [E, D, N1] / [E, F, D], got {tuple(w1.shape)} / "
-                         f"{tuple(w2.shape)}")
-    E, F = w2.shape[0], w2.shape[1]
-    N1 = 2 * F if act == 'swiglu' else F
-    if tuple(w1.shape) != (E, D, N1) or w2.shape[2] != D:
-        raise ValueError(f"moe_ffn: act = {act!r} over x {tuple(x.shape)} needs w1 [E, {D}, N1] and w2 [E, F, {D}] "
-                         f"with N1 = {'2F' if act == 'swiglu' else 'F'}, got w1 {tuple(w1.shape)} and w2 "
-                         f"{tuple(w2.shape)}")
+    wdt = None if weight_dtype is None else _wo_algo(weight_dtype)[0]
+    if wdt is not None:
+        E, F, N1, g = _moe_wo_check(x, w1, w2, w1_scale, w2_scale, act, wdt, group_size)
+    else:
+        if w1_scale is not None or w2_scale is not None:
+            raise ValueError(f"moe_ffn: w1_scale / w2_scale go with weight_dtype 'int8' / 'int4', got weight_dtype "
+                             f"= None with w1 {tuple(w1.shape)} and w2 {tuple(w2.shape)}")
+        if w2.dim() != 3 or w1.dim() != 3:
+            raise ValueError(f"moe_ffn: w1 / w2 must be [E, D, N1] / [E, F, D], got {tuple(w1.shape)} / "
+                             f"{tuple(w2.shape)}")
+        E, F = w2.shape[0], w2.shape[1]
+        N1 = 2 * F if act == 'swiglu' else F
+        if tuple(w1.shape) != (E, D, N1) or w2.shape[2] != D:
+            raise ValueError(f"moe_ffn: act = {act!r} over x {tuple(x.shape)} needs w1 [E, {D}, N1] and w2 "
+                             f"[E, F, {D}] with N1 = {'2F' if act == 'swiglu' else 'F'}, got w1 {tuple(w1.shape)} "
+                             f"and w2 {tuple(w2.shape)}")
     if ids.dim() != 2 or ids.shape[0] != M or tuple(weights.shape) != tuple(ids.shape) or ids.shape[1] > E:
         raise ValueError(f"moe_ffn: ids / weights must be [M = {M}, k <= E = {E}], got {tuple(ids.shape)} / "
                          f"{tuple(weights.shape)}")
     for name, b, n in (('b1', b1, N1), ('b2', b2, D)):
         if b is not None and b.numel() != E * n:
             raise ValueError(f"moe_ffn: {name} {tuple(b.shape)} has {b.numel()} values for [E = {E}, {n}]")
-    _check_dtypes('moe_ffn', (x, w1), (x, w2))
+    if wdt is None:
+        _check_dtypes('moe_ffn', (x, w1), (x, w2))
     b1 = None if b1 is None else b1.reshape(E, N1).to(x.dtype).contiguous()
     b2 = None if b2 is None else b2.reshape(E, D).to(x.dtype).contiguous()
-    a = _MOE_ACT[act]
+    a, op = _MOE_ACT[act], 'moe_ffn' if wdt is None else 'moe_ffn_wo'
+    args = (w1, w2, b1, b2, a) if wdt is None else (w1, w2, w1_scale, w2_scale, b1, b2, a, wdt, g)
     if _moe_in_limits(x2, E, ids.shape[1], D, F):
-        y = R.dispatch('moe_ffn', x2, _aligned(x2), ids.to(torch.int32).contiguous(),
-                       weights.float().contiguous(), w1.contiguous(), w2.contiguous(), b1, b2, a)
+        args = tuple(t.contiguous() if isinstance(t, torch.Tensor) else t for t in args)
+        y = R.dispatch(op, x2, _aligned(x2), ids.to(torch.int32).contiguous(), weights.float().contiguous(), *args)
     else:
-        R._STATS[('moe_ffn', 'ref')] += 1
-        y = _moe_ffn_ref(x2, ids, weights, w1, w2, b1, b2, a)
+        R._STATS[(op, 'ref')] += 1
+        y = R.get_kernel(op, 'ref')(x2, ids, weights, *args)
     return y.view(x.shape)

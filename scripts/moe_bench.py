@@ -1,8 +1,10 @@
 """Top-k routed MoE FFN at decode sizes on the GPU: the moe_ffn.hip kernels against the 'ref'
 composition and a byte floor.
 
-    python scripts/moe_bench.py [--quick] [--samples 5] [--tall]
+    python scripts/moe_bench.py [--quick] [--samples 5] [--tall | --wo]
 
+``--wo`` runs the decode cells over weight-only int8 / int4 expert weights (the moe_wo.hip kernel against
+the bf16 kernels, the fp32 'ref' and the quantised byte floor; see wo_cell).
 ``--tall`` runs the prefill cells instead (M = 512 and 4096, the moe_tall.hip kernels; see tall_cell).
 Decode cells: M = 8 and 32 tokens; E = 8 top-2 and E = 64 top-8; D = 2048; F = 1024 and 8192; SwiGLU; bf16.
 Three figures per cell:
@@ -72,6 +74,82 @@ def cell(M, E, k, D, F, quick, samples):
                           max_abs_diff_hip_ref=round(err, 5))), flush=True)
 
 
+WO_VARIANTS = (('int8', 'int8', -1), ('int4', 'int4', -1), ('int4 g128', 'int4', 128))
+
+
+def wo_cell(M, E, k, D, F, quick, samples):
+    """A decode cell over weight-only int8 / int4 experts (moe_wo.hip). Per variant, in the same run:
+    hip = route + moe_ffn(weight_dtype=...) from a graph over enough copies of the byte images to
+    exceed the last-level cache; bf16 = the moe_ffn.hip kernels from a graph over bf16 weights of the
+    same shapes; ref = the fp32 'ref' of the quantised op (dequantise each used expert), eager, one
+    copy; floor = the selected experts' quantised bytes and scales at ATTN_TBS. The byte images are
+    random bytes (every byte is a level, or two), since the time does not depend on the levels."""
+    from paddle_ray_amd.ops import fused as K
+    from paddle_ray_amd.ops import registry as R
+    dt, dev = torch.bfloat16, 'cuda'
+    torch.manual_seed(M + E + F)
+    x = torch.randn(M, D, device=dev).to(dt)
+    gw = torch.randn(D, E, device=dev) * D ** -0.5
+    active = int(K.moe_route(x, gw, k)[0].unique().numel())
+
+    def copies_of(per_expert):
+        return 2 if quick else max(1, -(-CACHE_BYTES // (E * per_expert)))
+
+    def timed(fn, copies):
+        R.reset_stats()
+        graph = _graph(fn)
+        assert all(b == 'hip' for _, b in R.stats()), R.stats()
+        return lambda: _time(graph.replay, 2 if quick else 10) / copies
+
+    with torch.no_grad():
+        nb = copies_of(3 * D * F * 2)
+        wb = [(torch.empty(E, D, 2 * F, device=dev, dtype=dt).normal_(0, D ** -0.5),
+               torch.empty(E, F, D, device=dev, dtype=dt).normal_(0, F ** -0.5)) for _ in range(nb)]
+
+        def bf16():
+            for w1, w2 in wb:
+                ids, w = K.moe_route(x, gw, k)
+                y = K.moe_ffn(x, ids, w, w1, w2)
+            return y
+        t_bf16 = timed(bf16, nb)
+        for name, wdt, g in WO_VARIANTS:
+            pk, qmax = (2, 7.0) if wdt == 'int4' else (1, 127.0)
+            s1 = torch.rand((E, D // g, 2 * F) if g > 0 else (E, 2 * F), device=dev) * (3 * D ** -0.5 / qmax)
+            s2 = torch.rand((E, F // g, D) if g > 0 else (E, D), device=dev) * (3 * F ** -0.5 / qmax)
+            per_expert = 3 * D * F // pk + 4 * (s1.numel() + s2.numel()) // E
+            nq = copies_of(per_expert)
+            wq = [(torch.randint(-128, 128, (E, 2 * F, D // pk), device=dev, dtype=torch.int8),
+                   torch.randint(-128, 128, (E, D, F // pk), device=dev, dtype=torch.int8)) for _ in range(nq)]
+            kw = dict(w1_scale=s1, w2_scale=s2, weight_dtype=wdt, group_size=g)
+
+            def hip():
+                for w1, w2 in wq:
+                    ids, w = K.moe_route(x, gw, k)
+                    y = K.moe_ffn(x, ids, w, w1, w2, **kw)
+                return y
+
+            def ref():
+                ids, w = K._moe_route_ref(x, gw, k, True)
+                return K._moe_ffn_wo_ref(x, ids, w, wq[-1][0], wq[-1][1], s1, s2, None, None, 4, wdt, g)
+            t_hip = timed(hip, nq)
+            err = float((hip().float() - ref().float()).abs().max())
+            times = {'hip': [], 'bf16': [], 'ref': []}
+            for _ in range(samples):
+                times['hip'].append(t_hip())
+                times['bf16'].append(t_bf16())
+                times['ref'].append(_time(ref, 1))
+            hip_us, bf16_us, ref_us = (_stats(times[n], 1e6) for n in ('hip', 'bf16', 'ref'))
+            floor_us = active * per_expert / (ATTN_TBS * 1e12) * 1e6
+            print(json.dumps(dict(wo=name, M=M, E=E, top_k=k, D=D, F=F, active_experts=active, weight_copies=nq,
+                                  bf16_copies=nb, selected_bytes=active * per_expert, hip_us=hip_us,
+                                  bf16_us=bf16_us, ref_us=ref_us, floor_us=round(floor_us, 2),
+                                  hip_over_floor=round(hip_us['median'] / floor_us, 2),
+                                  hip_over_bf16=round(hip_us['median'] / bf16_us['median'], 2),
+                                  ref_over_hip=round(ref_us['median'] / hip_us['median'], 2),
+                                  max_abs_diff_hip_ref=round(err, 5))), flush=True)
+            del wq
+
+
 GEMM_PFS = 1.51          # best bf16 rate of the project's training GEMM (README, MFMA GEMM row), PFLOP/s
 
 
@@ -133,6 +211,7 @@ def main():
     ap.add_argument('--quick', action='store_true', help='small cells, two copies: a rehearsal, not a measurement')
     ap.add_argument('--samples', type=int, default=5)
     ap.add_argument('--tall', action='store_true', help='the prefill cells (M 512 and 4096) instead of the decode ones')
+    ap.add_argument('--wo', action='store_true', help='the decode cells over weight-only int8 / int4 experts')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("moe_bench: no GPU (the measurement does not fall back to the CPU)")
@@ -147,10 +226,11 @@ def main():
                     tall_cell(M, E, k, 2048, F, False, a.samples)
                 torch.cuda.empty_cache()
             for M in () if a.tall else (8, 32):
+                run = wo_cell if a.wo else cell
                 if a.quick:
-                    cell(M, E, k, 256, F // 8, True, 1)
+                    run(M, E, k, 256, F // 8, True, 1)
                 else:
-                    cell(M, E, k, 2048, F, False, a.samples)
+                    run(M, E, k, 2048, F, False, a.samples)
                 torch.cuda.empty_cache()
 
 
